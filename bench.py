@@ -27,14 +27,23 @@ every accumulator (acceptance, exact moments, the lag sums), inside the timed
 region.  The 8-GPU workload of BASELINE configs[3] is
 ``--gpus 8 --config C4_qary1024`` (2^15 chains per GPU, 2^18 in all).
 
-Also reported: the dominant kernel's roofline (the Klein sampler: executed-work
+A plain run sets up, warms up, times --steps bench steps and prints the result
+line: the headline figure with what the timed steps themselves yield (acceptance,
+certificate redo count, lag sums, covariance, per-kernel HIP-event times, memory).
+``--dump-outputs DIR`` then writes what the last timed step and the final reduce
+returned to their caller as DIR/<name>.npy (``dump_outputs``); the inputs are a
+function of the arguments alone (Philox counters), so two builds can be compared
+array by array.
+
+With ``--full`` also reported: the dominant kernel's roofline (the Klein sampler: executed-work
 and HBM counters and the launch's rocprof duration from the committed rocprofv3
 profile of this command, profiles/r0*_klein_counters.json, used only when its
 build_id is the loaded library's; the HIP-event time of the same kernel in this
-run beside it), the
-certificate's redo count, a parity check of the timed run's final chain states
-against the oracle, and the CPU baselines (the C oracle over the host cores and
-the NumPy restatement of the reference's loop, one process per core).
+run beside it), a parity check of the timed run's final chain states
+against the oracle, the Wang-Ling leg, and the CPU baselines (the C oracle over
+the host cores and the NumPy restatement of the reference's loop, one process per
+core).  The options that shape those legs (--cpu-samples, --wl-steps, --no-cpu,
+--counters, ...) act under ``--full`` only.
 """
 import argparse
 import glob
@@ -56,6 +65,11 @@ FP64_PEAK_TFLOPS = 78.6    # MI355X FP64 vector / matrix dense peak (spec)
 I8_PEAK_TOPS = 5000.0      # MI355X int8 MFMA dense (2x BF16 per clock, MI355X_MICROARCH.md)
 ACF_LAGS = 16              # lag-L autocovariance of z_{d-1} and ||v||^2
 ACF_CHAINS = 1024          # chains per rank whose states feed the lag sums
+DUMP_SEED = 0xD0E5         # --dump-outputs: the sampled chains / steps (fixed)
+DUMP_Z_ELEMS = 1 << 20     # elements of the sampled final states (8 MB as fp64)
+DUMP_V_ELEMS = 1 << 21     # elements of the sampled lattice points of the last step (16 MB)
+DUMP_V_STEPS = 8           # steps of the last block whose lattice points are sampled
+DUMP_GRAM_DIM = 2048       # leading block of sum z z^T written (32 MB; all of it for d <= 2048)
 
 WORKLOADS = {
     "C3_ntru512": dict(chains=1 << 14, text="NTRU n=512 q=12289 d=1024 sigma=165.7 IMHK"),
@@ -78,19 +92,25 @@ def parse():
     ap.add_argument("--no-v", action="store_true", help="skip lattice points (coefficients only)")
     ap.add_argument("--exact-order", action="store_true")
     ap.add_argument("--cpu-samples", type=int, default=0,
-                    help="IMHK proposals for the C-port baseline (0: 512 per core, < 0: skip it)")
+                    help="with --full: IMHK proposals for the C-port baseline (0: 512 per core, < 0: skip it)")
     ap.add_argument("--wl-steps", type=int, default=3,
-                    help="timed bench steps of the Wang-Ling leg after the headline (0: skip)")
+                    help="with --full: timed bench steps of the Wang-Ling leg after the headline (0: skip)")
     ap.add_argument("--wl-check-chains", type=int, default=8,
-                    help="chains of the Wang-Ling leg replayed by the C oracle")
-    ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--numpy-samples", type=int, default=24, help="Klein samples per process, NumPy baseline")
-    ap.add_argument("--no-cpu", action="store_true")
+                    help="with --full: chains of the Wang-Ling leg replayed by the C oracle")
+    ap.add_argument("--cpu-threads", type=int, default=0,
+                    help="with --full: threads / processes of the CPU baselines (0: this process's CPU share)")
+    ap.add_argument("--numpy-samples", type=int, default=24, help="with --full: Klein samples per process, NumPy baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-dist", action="store_true", help="N = 1 without the one-rank RCCL group")
     ap.add_argument("--gram-every", type=int, default=1,
                     help="exact sum z z^T of the chains' states after every k-th bench step (0: off)")
     ap.add_argument("--counters", default=os.environ.get("LGS_COUNTERS_JSON", ""),
-                    help="klein_counters.json of a rocprofv3 profile of this command (default: newest in profiles/)")
+                    help="with --full: klein_counters.json of a rocprofv3 profile of this command "
+                         "(default: newest in profiles/)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: oracle parity check, roofline, Wang-Ling leg, CPU baselines")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs and the reduced statistics as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -166,6 +186,50 @@ def load_counters(path, config, bid):
     if bid is None or cnt.get("build_id") != bid:
         return None, rel, "stale"
     return cnt, rel, "current"
+
+
+def dump_outputs(path, torch, advance, shard, stats):
+    """What the timed path handed its caller, as path/<name>.npy (float64; integers
+    there are below 2^53, so exact): the last timed step's outputs (advance.state
+    after shard.step: chain states z, log weights, the kept lattice points v and the
+    two lag functionals) and the reduced statistics of all timed steps
+    (shard.reduce()).  Everything per chain (z, log weights, accept counts, v) is
+    taken at a fixed seeded sample of chains, everything per step of the block (v --
+    alone chains x steps x d fp64 -- and the two functionals, whose rows are the
+    leading ACF_CHAINS chains) at a seeded sample of steps that always holds the
+    block's last step (the chains' final state), and sum z z^T is cut to its leading
+    DUMP_GRAM_DIM block: the files stay under 64 MB whatever --chains and
+    --imhk-steps are (about 34 MB at d = 1024).  sample_chains / sample_chains_v /
+    sample_steps hold the indices."""
+    os.makedirs(path, exist_ok=True)
+    st = advance.state
+    nc, d = shard.nc, shard.d
+    rng = np.random.default_rng(DUMP_SEED)
+    chains = np.sort(rng.choice(nc, size=min(nc, max(1, DUMP_Z_ELEMS // d)), replace=False))
+    ch = torch.as_tensor(chains, device=st["z"].device)
+    out = {"sample_chains": chains,
+           "z_state": st["z"].index_select(1, ch).t(),          # (sampled chains, d)
+           "log_weight": st["lw"][ch], "accepts_per_chain": shard.acc[ch],
+           "accepts": stats["accepts"], "moments": stats["moments"]}
+    if st["v"] is not None:
+        T = st["v"].shape[1]
+        steps = np.sort(np.append(rng.choice(T - 1, size=min(T, DUMP_V_STEPS) - 1, replace=False), T - 1))
+        vch = chains[:max(1, DUMP_V_ELEMS // (len(steps) * d))]
+        sp = torch.as_tensor(steps, device=ch.device)
+        out.update({"sample_steps": steps, "sample_chains_v": vch,
+                    "v_last_step": st["v"][torch.as_tensor(vch, device=ch.device)[:, None], sp[None, :]],
+                    "zk_last_step": st["zk"][:ACF_CHAINS].index_select(1, sp),
+                    "vnorm2_last_step": st["vn2"][:ACF_CHAINS].index_select(1, sp)})
+    for name in ("lag_z", "lag_v"):
+        for part, x in zip(("S", "N", "S1", "n"), stats[name]):
+            out[f"{name}_{part}"] = x
+    if "gram" in stats:
+        g = min(d, DUMP_GRAM_DIM)
+        out.update({"gram_sum_zzT": stats["gram"][0][:g, :g], "gram_sum_z": stats["gram"][1], "gram_states": stats["gram"][2]})
+    for name, x in out.items():
+        if torch.is_tensor(x):
+            x = x.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(x, dtype=np.float64))
 
 
 def wang_ling_leg(args, ctx, D, _capi, lgs_oracle, R, cp, B, sigma, d, nc, T, seed, dev, binv_k):
@@ -314,6 +378,8 @@ def main():
               "torch_peak_reserved_gib_per_rank": round(mem_t[1], 1),
               "ranks_on_device": world if os.environ.get("LGS_ONE_DEVICE") == "1" else 1}
     step_counter = [shard.next_step]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, advance, shard, stats)
 
     proposals = args.steps * nc * T * world
     value = proposals / elapsed
@@ -337,6 +403,62 @@ def main():
                       "sum_zzT_sha256": hashlib.sha256(np.ascontiguousarray(G).tobytes()).hexdigest()[:16],
                       "trace": float(np.trace(cov)), "offdiag_abs_max": float(np.abs(cov - np.diag(np.diag(cov))).max()),
                       "diag_min": float(np.diag(cov).min()), "diag_max": float(np.diag(cov).max())}
+
+    gemm = None
+    if g_n:
+        gemm = {"kernel": "bz_i8_kernel", "ms_per_step": round(g_ms / args.steps, 3)}
+        if pipelined:
+            gemm["note"] = ("HIP-event span on the work stream, beside the next block's Klein launch (pipelined "
+                            "blocks): it stretches over that launch; LGS_NO_PIPE=1 times it alone")
+    dinfo = ctx.device_info()
+    # ---- the result line of a plain run: the headline and what the timed steps
+    # themselves yielded; --full adds its legs' keys below
+    out = {
+        "metric": "Klein samples/sec at n=512 NTRU (IMHK proposals, d=1024)" if args.config == "C3_ntru512"
+        else f"Klein samples/sec, {args.config} (IMHK proposals, d={d})",
+        "value": round(value, 1),
+        "unit": "samples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (Philox-generated basis, seed 1)",
+        "config": {"workload": f"{args.config}: {WORKLOADS[args.config]['text']}",
+                   "chains_per_gpu": nc, "chains_total": nc * world, "imhk_steps_per_step": T, "thin": 1,
+                   "lattice_points": not args.no_v, "kernel_order": "exact" if args.exact_order else "certified-blocked",
+                   "parallelism": f"chains sharded over {world} GPU(s); one all-reduce of every accumulator "
+                                  f"after the timed steps (inside the timed region)",
+                   "collective": collective},
+        "imhk_acceptance": round(acceptance, 6),
+        # (reference mode: the weight is a constant up to rounding, acceptance 1; the
+        # Wang-Ling leg of --full carries the acceptance that can differ)
+        "certificate_redos": {"verified_subpanels": redos, "per_proposal": redos / (args.steps * nc * T)},
+        "autocorrelation": acf,
+        "covariance": covariance,
+        "gemm": gemm,
+        "memory": memory,
+        "kernel_ms": {"klein": round(k_ms / max(k_n, 1), 3), "bz": round(g_ms / max(g_n, 1), 3),
+                      "accept": round(a_ms / max(a_n, 1), 3), "moments": round(m_ms / max(m_n, 1), 3),
+                      "blocks_pipelined": pipelined,
+                      "klein_stream_cus": ctx.counter(_capi.LGS_COUNTER_KLEIN_CUS) or dinfo.get("n_cu"),
+                      "note": "pipelined blocks: each lgs_imhk block's Klein launch runs on the library's Klein "
+                              "stream beside the previous block's accept / moments / B z on the work stream, so "
+                              "these launch times overlap (their sum exceeds ms_per_step) and each is stretched by "
+                              "sharing the CUs; the Klein stream's queue is masked to klein_stream_cus CUs "
+                              "(1/8 of them left to B z); LGS_NO_PIPE=1 gives isolated launches"},
+        "device": dinfo["name"],
+        "full": args.full,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if D.collective_active():
+            dist.destroy_process_group()
+        return
 
     # ---- parity: the timed run's final chain states against the oracle.  In the
     # reference's IMHK mode every proposal is accepted (the weight is a constant up to
@@ -407,12 +529,6 @@ def main():
     roofline["hbm_algorithmic_note"] = (
         f"SURVEY 8d B_alg = {b_alg(d)} B/sample counts R once per sample, but R is shared by every "
         f"chain (read once per 256-sample block from L2), so B_alg x rate is not an HBM quantity")
-    gemm = None
-    if g_n:
-        gemm = {"kernel": "bz_i8_kernel", "ms_per_step": round(g_ms / args.steps, 3)}
-        if pipelined:
-            gemm["note"] = ("HIP-event span on the work stream, beside the next block's Klein launch (pipelined "
-                            "blocks): it stretches over that launch; LGS_NO_PIPE=1 times it alone")
 
     # ---- Wang-Ling leg (after the headline's timed region; not part of `value`):
     # the one IMHK mode whose acceptance is not identically 1 (imhk.py:102-124 gives a
@@ -462,51 +578,13 @@ def main():
                 "calibration": "restatement / imported reference = 1.051 per core on the same C3 basis and "
                                "samples (profiles/r03_cpu_baseline_calibration.log)"})
 
-    dinfo = ctx.device_info()
-    out = {
-        "metric": "Klein samples/sec at n=512 NTRU (IMHK proposals, d=1024)" if args.config == "C3_ntru512"
-        else f"Klein samples/sec, {args.config} (IMHK proposals, d={d})",
-        "value": round(value, 1),
-        "unit": "samples/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (Philox-generated basis, seed 1)",
-        "config": {"workload": f"{args.config}: {WORKLOADS[args.config]['text']}",
-                   "chains_per_gpu": nc, "chains_total": nc * world, "imhk_steps_per_step": T, "thin": 1,
-                   "lattice_points": not args.no_v, "kernel_order": "exact" if args.exact_order else "certified-blocked",
-                   "parallelism": f"chains sharded over {world} GPU(s); one all-reduce of every accumulator "
-                                  f"after the timed steps (inside the timed region)",
-                   "collective": collective},
-        "imhk_acceptance": round(acceptance, 6),
+    out.update({
         "imhk_acceptance_cpu_reference": None if cpu is None else cpu["acceptance"],
-        # (reference mode: the weight is a constant up to rounding, acceptance 1; the
-        # Wang-Ling leg below carries the acceptance that can differ)
         "parity_check": parity,
-        "certificate_redos": {"verified_subpanels": redos, "per_proposal": redos / (args.steps * nc * T)},
-        "autocorrelation": acf,
-        "covariance": covariance,
         "roofline": roofline,
-        "gemm": gemm,
-        "memory": memory,
-        "kernel_ms": {"klein": round(k_ms / max(k_n, 1), 3), "bz": round(g_ms / max(g_n, 1), 3),
-                      "accept": round(a_ms / max(a_n, 1), 3), "moments": round(m_ms / max(m_n, 1), 3),
-                      "blocks_pipelined": pipelined,
-                      "klein_stream_cus": ctx.counter(_capi.LGS_COUNTER_KLEIN_CUS) or dinfo.get("n_cu"),
-                      "note": "pipelined blocks: each lgs_imhk block's Klein launch runs on the library's Klein "
-                              "stream beside the previous block's accept / moments / B z on the work stream, so "
-                              "these launch times overlap (their sum exceeds ms_per_step) and each is stretched by "
-                              "sharing the CUs; the Klein stream's queue is masked to klein_stream_cus CUs "
-                              "(1/8 of them left to B z); LGS_NO_PIPE=1 gives isolated launches"},
         "cpu_baseline": cpu,
         "wang_ling": wang_ling,
-        "device": dinfo["name"],
-    }
+    })
     print(json.dumps(out))
     if D.collective_active():
         dist.destroy_process_group()

@@ -88,6 +88,62 @@ def test_gloo_world2_lag_sums_match_single_process():
         assert S1 == single.S1.tolist() and n == [single.n]
 
 
+def test_dump_outputs_writes_what_the_caller_received(tmp_path, monkeypatch):
+    """bench.py --dump-outputs over a host stand-in for gpu_advance: float64 files of
+    the last step's state and the reduced statistics; per-chain and per-step arrays at
+    the seeded sample of chains / steps named by the index files (the last step always
+    among them); the same sample on a second call; T = 1 works."""
+    nc, T, d = 12, 5, 4
+    rng = np.random.default_rng(1)
+    st = {"z": torch.from_numpy(rng.integers(-9, 9, (d, nc)).astype(np.int32)),
+          "lw": torch.from_numpy(rng.standard_normal(nc)),
+          "v": torch.from_numpy(rng.integers(-99, 99, (nc, T, d)).astype(np.float64)),
+          "zk": torch.from_numpy(rng.integers(-9, 9, (nc, T))),
+          "vn2": torch.from_numpy(rng.random((nc, T)))}
+
+    def advance(first_step, n_steps, acc, mom):
+        acc += 1 + torch.arange(nc)
+        return {"v": st["v"], "zk": st["zk"], "vn2": st["vn2"]}
+
+    def gram(G, S):
+        z = st["z"].long()
+        G += z @ z.t()
+        S += z.sum(1)
+
+    advance.state, advance.gram = st, gram
+    shard = D.StreamingShard(advance, nc, d, binv_row=np.ones(d), device="cpu", lag_chains=nc, lags=3, gram_every=1)
+    shard.step(T)
+    stats = shard.reduce()
+    monkeypatch.setattr(bench, "DUMP_Z_ELEMS", 6 * d)
+    monkeypatch.setattr(bench, "DUMP_V_ELEMS", 3 * 2 * d)
+    monkeypatch.setattr(bench, "DUMP_V_STEPS", 2)
+    outs = []
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), torch, advance, shard, stats)
+        outs.append({f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))})
+    a, b = outs
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert all(x.dtype == np.float64 for x in a.values())
+    ch, vch, steps = (a[k].astype(int) for k in ("sample_chains", "sample_chains_v", "sample_steps"))
+    assert len(ch) == 6 and len(vch) == 3 and len(steps) == 2 and len(set(ch)) == 6
+    np.testing.assert_array_equal(a["z_state"], st["z"].numpy().T[ch])
+    np.testing.assert_array_equal(a["v_last_step"], st["v"].numpy()[vch][:, steps])
+    assert steps[-1] == T - 1  # the block's last step: the chains' final state
+    np.testing.assert_array_equal(a["zk_last_step"], st["zk"].numpy()[:, steps])
+    np.testing.assert_array_equal(a["vnorm2_last_step"], st["vn2"].numpy()[:, steps])
+    np.testing.assert_array_equal(a["log_weight"], st["lw"].numpy()[ch])
+    np.testing.assert_array_equal(a["accepts_per_chain"], 1 + ch)
+    z = st["z"].numpy().astype(np.int64)
+    np.testing.assert_array_equal(a["gram_sum_zzT"], z @ z.T)
+    assert a["accepts"].tolist() == [nc * (nc + 1) // 2] and a["gram_states"].tolist() == [nc]
+    assert a["lag_z_S"].shape == (4,) and a["lag_v_N"].shape == (4,)
+    for k in ("v", "zk", "vn2"):  # a one-step block: its only step is the sample
+        st[k] = st[k][:, :1].contiguous()
+    bench.dump_outputs(str(tmp_path / "c"), torch, advance, shard, stats)
+    assert np.load(tmp_path / "c" / "sample_steps.npy").tolist() == [0]
+    assert np.load(tmp_path / "c" / "v_last_step.npy").shape == (6, 1, d)  # (the element budget: more chains)
+
+
 def test_counters_used_only_for_the_same_build(tmp_path):
     import json
     p = tmp_path / "x_klein_counters.json"

@@ -1,15 +1,16 @@
 # Profile of the bench command for bench.py's roofline: rocprofv3 kernel trace +
 # --stats, then separate --pmc passes (SQ instruction mix, issue/wait, FETCH_SIZE,
-# WRITE_SIZE) under gpurun_out/prof_TAG; then, in the container, summarise into
-# profiles/: python3 tools/summarize_prof.py gpurun_out/prof_TAG TAG and
-# python3 tools/roofline_counters.py gpurun_out/prof_TAG CFG UNITS D profiles/TAG_klein_counters.json
+# WRITE_SIZE) under $OUT/prof_TAG (OUT defaults to out); then summarise into
+# profiles/: python3 tools/summarize_prof.py $OUT/prof_TAG TAG and
+# python3 tools/roofline_counters.py $OUT/prof_TAG CFG UNITS D profiles/TAG_klein_counters.json
 # usage: bash tools/gpu_roofline.sh TAG [config]
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 TAG=${1:-r02}
 CFG=${2:-C3_ntru512}
-ARGS="--steps 3 --warmup 1 --no-cpu --wl-steps 0 --config $CFG"
+# (--full: the result line's roofline.units_per_launch / build_id are read below)
+ARGS="--full --steps 3 --warmup 1 --no-cpu --wl-steps 0 --config $CFG"
 # Isolated launches (round 5): the bench pipelines each block's Klein launch beside the
 # previous block's B z; under rocprofv3 that overlap changes (the profiled bench ran at
 # 93.8 instead of 105 M samples/s, its Klein launches stretched to 10.0 ms by both
@@ -17,7 +18,7 @@ ARGS="--steps 3 --warmup 1 --no-cpu --wl-steps 0 --config $CFG"
 # same command with LGS_NO_PIPE=1, where each launch has the chip to itself
 # (PROF_NO_PIPE=0: profile the pipelined command)
 export LGS_NO_PIPE=${PROF_NO_PIPE:-1}
-O=gpurun_out/prof_$TAG
+O=${OUT:-out}/prof_$TAG
 mkdir -p $O profiles
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 bench.py $ARGS > $O/bench_trace.log 2>&1 || { tail -20 $O/bench_trace.log; exit 1; }
 P1="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU"
