@@ -187,12 +187,13 @@ struct lgs_ctx {
     int zint = 2;  // internal coefficient store width (bytes): 16-bit, sticky 32-bit on overflow; LGS_ZINT=4 forces 32-bit
     // timing
     bool timing = false;
-    double t_ms[7] = {0, 0, 0, 0, 0, 0, 0};
-    int64_t t_n[7] = {0, 0, 0, 0, 0, 0, 0};
+    double t_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t t_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // diagnostics scratch (lgs_series_stats / lgs_gram / lgs_jump_distance / lgs_marginal_tvd)
     DevBuf dg_x, dg_y, dg_out, dg_a, dg_b, dg_c, dg_t;
     // decoding frame (lgs_set_decoder): Q of the QR and (B^{-1})^T, row-major d x d
     DevBuf DQ, DBIT;
+    DevBuf CPT;  // lgs_klein_targets: the chunk's centres c' = Q^T t, coordinate-major, padded to whole waves
     bool has_q = false, has_binv = false;
     std::vector<Timer> pending;
     std::vector<hipEvent_t> pool;
@@ -2066,7 +2067,7 @@ int lgs_timing_enable(lgs_ctx* c, int enable) {
         fold_timers(c);
     }
     c->timing = enable != 0;
-    for (int k = 0; k < 7; ++k) {
+    for (int k = 0; k < 8; ++k) {
         c->t_ms[k] = 0;
         c->t_n[k] = 0;
     }
@@ -2075,7 +2076,7 @@ int lgs_timing_enable(lgs_ctx* c, int enable) {
 
 int lgs_timing_get(lgs_ctx* c, int kernel, double* ms, int64_t* n) {
     if (!c) return fail(LGS_ERR_INVALID, "null context");
-    if (kernel < 0 || kernel > 6) return fail(LGS_ERR_INVALID, "kernel id 0..6");
+    if (kernel < 0 || kernel > 7) return fail(LGS_ERR_INVALID, "kernel id 0..7");
     if (!c->pending.empty()) {  // launches of an early-checked call may still be running
         int rc = check_ctx(c, false);
         if (rc) return rc;
@@ -2576,6 +2577,122 @@ int lgs_nearest_plane(lgs_ctx* c, int64_t n, const double* targets, void* z_out,
 int lgs_round_decode(lgs_ctx* c, int64_t n, const double* targets, void* z_out, double* v_out,
                      uint32_t flags) {
     return run_decode(c, false, n, targets, z_out, v_out, flags);
+}
+
+// Klein draws around one centre per sample.  Per chunk of max_proposals targets: the
+// centres c' = Q^T t (or the caller's c') coordinate-major in CPT, padded with zeros to
+// whole waves (m -> mp lanes, timer 7); the draw into a coefficient store of the output
+// width with mp columns (timer 0); then z / v / c' outputs of the first m columns as
+// lgs_klein and run_decode write them.  Padded lanes draw around c' = 0 into columns
+// the outputs never read.
+int lgs_klein_targets(lgs_ctx* c, uint64_t seed, uint64_t first, int64_t n, const double* targets,
+                      void* z_out, double* v_out, double* cprime_out, uint32_t flags) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (flags & ~(uint32_t)(LGS_DEVICE_PTRS | LGS_Z64 | LGS_COORD_MAJOR | LGS_EXACT_ORDER | LGS_TARGETS_QFRAME))
+        return fail(LGS_ERR_INVALID, "lgs_klein_targets: unsupported flag 0x%x", flags);
+    if (n < 0) return fail(LGS_ERR_INVALID, "n < 0");
+    if (n == 0) return LGS_OK;
+    if (!targets) return fail(LGS_ERR_INVALID, "null targets");
+    const bool dev = flags & LGS_DEVICE_PTRS, z64 = flags & LGS_Z64, cm = flags & LGS_COORD_MAJOR,
+               exact = flags & LGS_EXACT_ORDER, qframe = flags & LGS_TARGETS_QFRAME;
+    if (!qframe && (!c->has_q || c->DQ.bytes < (size_t)c->d * c->d * 8))
+        return fail(LGS_ERR_STATE, "targets in the lattice frame need Q (lgs_set_decoder)");
+    if (v_out && !c->has_B) return fail(LGS_ERR_STATE, "v_out requires B");
+    const int64_t d = c->d;
+    const int ob = z64 ? 8 : 4;
+    if ((rc = reset_flags(c))) return rc;
+    const int64_t chunk = std::min<int64_t>(n, c->max_props);
+    const int64_t chunk_p = (chunk + 63) / 64 * 64;
+    if ((rc = c->CPT.reserve((size_t)chunk_p * d * 8)) || (rc = c->Z.reserve((size_t)chunk_p * d * ob))) return rc;
+    if (!qframe && ((rc = c->dg_x.reserve((size_t)chunk * d * 8)) || (rc = c->dg_y.reserve((size_t)chunk * d * 8))))
+        return rc;
+    if (!dev) {
+        if ((rc = c->stage_a.reserve((size_t)chunk * d * 8))) return rc;
+        if (cprime_out && (rc = c->stage_b.reserve((size_t)chunk * d * 8))) return rc;
+        if (v_out && (rc = c->V.reserve((size_t)chunk * d * 8))) return rc;
+    }
+    double dmu_scale = 1.0;
+    // test hook (the knob of the 32-row-panel kernels' cap): a scale s < 1 widens every
+    // certificate bound by 1 / s, so decisions go through the reference-order path
+    if (const char* s = hook("LGS_TEST_Z1CAP_SCALE")) {
+        const double v = atof(s);
+        if (v > 0.0 && v < 1.0) dmu_scale = 1.0 / v;
+    }
+    double* X = c->CPT.as<double>();
+    for (int64_t off = 0; off < n; off += chunk) {
+        const int64_t m = std::min<int64_t>(chunk, n - off);
+        const int64_t mp = (m + 63) / 64 * 64;
+        {
+            Scope s(c, 7);
+            if (mp > m) HIP_TRY(hipMemset2DAsync(X + m, (size_t)mp * 8, 0, (size_t)(mp - m) * 8, (size_t)d, c->stream));
+            if (qframe && cm) {
+                HIP_TRY(hipMemcpy2DAsync(X, (size_t)mp * 8, targets + off, (size_t)n * 8, (size_t)m * 8, (size_t)d,
+                                         kind_of(true, dev), c->stream));
+            } else {
+                const double* src;  // row-major m x d on the device
+                if (cm) {           // lattice frame, coordinate-major: T (d x m) for the GEMM
+                    HIP_TRY(hipMemcpy2DAsync(c->dg_x.p, (size_t)m * 8, targets + off, (size_t)n * 8, (size_t)m * 8,
+                                             (size_t)d, kind_of(true, dev), c->stream));
+                    src = nullptr;
+                } else {
+                    src = targets + (size_t)off * d;
+                    if (!dev) {
+                        HIP_TRY(hipMemcpyAsync(c->stage_a.p, src, (size_t)m * d * 8, hipMemcpyHostToDevice, c->stream));
+                        src = c->stage_a.as<double>();
+                    }
+                    if (!qframe) HIP_TRY(lgs::launch::to_coord_major(src, 8, m, (int)d, c->dg_x.p, 8, m, c->stream));
+                }
+                if (!qframe) {
+                    HIP_TRY(lgs::launch::gemm_f64(c->dg_x.as<double>(), m, c->DQ.as<double>(), (int)d, m,
+                                                  c->dg_y.as<double>(), c->stream));
+                    src = c->dg_y.as<double>();
+                }
+                HIP_TRY(lgs::launch::to_coord_major(src, 8, m, (int)d, X, 8, mp, c->stream));
+            }
+        }
+        lgs::KleinArgs a = base_args(c, seed);
+        a.counter_mode = 0;
+        a.base = first + (uint64_t)off;
+        a.n = mp;
+        a.ldz = mp;
+        void* Zp = c->Z.p;
+        {
+            Scope s(c, 0);
+            c->hist.Z = nullptr;  // (no int16 history: B z reads the store)
+            HIP_TRY(lgs::launch::klein_targets(a, c->R.as<double>(), c->RP.as<double>(), c->RC.as<double>(), c->panel,
+                                               exact, X, mp, dmu_scale, ob, Zp, c->stream));
+        }
+        if (z_out) {
+            if (cm) {
+                HIP_TRY(hipMemcpy2DAsync((char*)z_out + (size_t)off * ob, (size_t)n * ob, Zp, (size_t)mp * ob,
+                                         (size_t)m * ob, (size_t)d, kind_of(dev, true), c->stream));
+            } else {
+                void* dst = dev ? (char*)z_out + (size_t)off * d * ob : c->stage_a.p;
+                HIP_TRY(lgs::launch::transpose_out(Zp, ob, mp, m, (int)d, dst, ob, c->stream));
+                if (!dev)
+                    HIP_TRY(hipMemcpyAsync((char*)z_out + (size_t)off * d * ob, dst, (size_t)m * d * ob,
+                                           hipMemcpyDeviceToHost, c->stream));
+            }
+        }
+        if (cprime_out) {  // row-major, the centres the kernel read
+            void* dst = dev ? (void*)(cprime_out + (size_t)off * d) : c->stage_b.p;
+            HIP_TRY(lgs::launch::transpose_out(X, 8, mp, m, (int)d, dst, 8, c->stream));
+            if (!dev)
+                HIP_TRY(hipMemcpyAsync(cprime_out + (size_t)off * d, dst, (size_t)m * d * 8, hipMemcpyDeviceToHost,
+                                       c->stream));
+        }
+        if (v_out) {
+            double* V = dev ? v_out + (size_t)off * d : c->V.as<double>();
+            if ((rc = run_bz(c, Zp, ob, mp, m, V))) return rc;
+            if ((rc = settle_bz(c))) return rc;
+            if (!dev)
+                HIP_TRY(hipMemcpyAsync(v_out + (size_t)off * d, V, (size_t)m * d * 8, hipMemcpyDeviceToHost,
+                                       c->stream));
+        }
+        if ((rc = finish(c))) return rc;
+    }
+    return finish(c);
 }
 
 }  // extern "C"

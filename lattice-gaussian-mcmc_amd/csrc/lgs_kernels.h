@@ -391,6 +391,13 @@ hipError_t gemm_f64(const double* X, int64_t ldx, const double* MT, int d, int64
 hipError_t nearest_plane(int d, int64_t n, int panel, const double* RP, const double* RC,
                          const double* rii, const double* CP, int64_t ldc, int zb, void* Z, int64_t ldz,
                          unsigned int* flags, hipStream_t st);
+// Klein draws around per-sample centres CP (coordinate-major, CP[i * ldc + p], every lane of
+// [0, a.n) readable; zb 4 or 8).  exact: the reference's order; else the blocked certified
+// kernel, fp64 MFMA far field (a.n % 64 == 0, a.ldz % 4 == 0, Z 16-byte aligned);
+// dmu_scale multiplies the certificate's bound (1; > 1 forces reference-order decisions)
+hipError_t klein_targets(const KleinArgs& a, const double* R, const double* RP, const double* RC, int panel,
+                         bool exact, const double* CP, int64_t ldc, double dmu_scale, int zb, void* Z,
+                         hipStream_t st);
 hipError_t round_coeffs(const double* W, int64_t ldw, int d, int64_t n, int zb, void* Z, int64_t ldz,
                         unsigned int* flags, hipStream_t st);
 hipError_t check_range16(const void* zs, int ob, int64_t count, unsigned int* flags, hipStream_t st);

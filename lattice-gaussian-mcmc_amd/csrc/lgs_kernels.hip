@@ -2221,6 +2221,201 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? LGS_OZ_LB : LGS_MFMA_LB32) : 
 #endif
 }
 
+// ------------------------------------------------------------ per-sample centres
+// Klein's sampler around one centre per sample (lgs_klein_targets): the draw of
+// klein.py:181-220 with c' = Q^T t_s of the lane's own target, read coordinate-major
+// (CP[i * ldc + p]: one coalesced 8-byte load per coordinate per lane) where the
+// kernels above read the context's per-coordinate constant a.cp.  Sigma, precision
+// and every SampleZ constant come from the loaded basis; no weights.
+
+// resolve_coord with the lane's own centre: the decision of coordinate i redone at
+// the reference-order mean (c'_i - sum_{j>i} R_ij z_j) / R_ii, same uniform.
+template <typename ZT>
+__device__ __forceinline__ double resolve_coord(const KleinArgs& a, int i, double cpl, const ZT* Zp, size_t ldz,
+                                                CoordStream& rs, unsigned int& flags) {
+    const size_t iq = (size_t)i * kSzcStride;
+    const Resolved r = resolve_decision(a.R, Zp, ldz, i, a.d, cpl, cst(a.rii)[i],
+                                        a.szc ? a.szc + iq : nullptr,
+                                        a.szc ? cst(a.szc)[iq] : cst(a.sig)[i], rs.u((uint32_t)(a.d - 1 - i)),
+                                        a.precision, a.linear_probs != 0, false, a.etab,
+                                        a.flags + kFlagWordResolved);
+    if (!isfinite(r.mu)) {
+        flags |= kFlagNonFinite;
+        return 0.0;
+    }
+    return r.z;
+}
+
+// klein_exact_kernel with a per-lane centre: sequential j-ascending unfused sums
+// (klein.py:191-193).  Every lane of [0, a.n) is drawn: the caller pads CP and Z.
+template <typename ZT>
+__global__ __launch_bounds__(256) void klein_targets_exact_kernel(const KleinArgs a,
+                                                                  const double* __restrict__ R,
+                                                                  const double* __restrict__ CP, int64_t ldc,
+                                                                  ZT* __restrict__ Z) {
+    __shared__ double tab_lds[2 * (kErfTabLast + 1)];
+    const lds_cdptr etab_s = stage_etab(tab_lds, a.etab);
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.n) return;
+    uint32_t chain, step;
+    lane_counter(a, p, chain, step);
+    CoordStream rs;
+    rs.init(a.seed, step, chain);
+    const int d = a.d;
+    const size_t ldz = (size_t)a.ldz;
+    double lw = 0.0, eb = 0.0, tb = 0.0;
+    unsigned int flags = 0;
+    for (int i = d - 1; i >= 0; --i) {
+        const double* __restrict__ Ri = R + (size_t)i * d;
+        const double cpl = CP[(size_t)i * ldc + p];
+        double cs = 0.0;
+        for (int j = i + 1; j < d; ++j) cs = cs + Ri[j] * (double)Z[(size_t)j * ldz + p];
+        const double mu = (cpl - cs) / a.rii[i];
+        const double zi = decide_coord<false>(a, i, mu, rs, lw, flags, etab_s, -1.0, eb, tb);
+        store_z(Z, (size_t)i * ldz + p, zi, flags);
+    }
+    if (flags) atomicOr(a.flags, flags);
+}
+
+// Blocked, certified: the panel layout of klein_panel_kernel (RP / RC, PB = 16 or 32
+// rows), the far field of each panel on v_mfma_f64_16x16x4_f64 with the fragment
+// layout and the 4-stage load pipeline of klein_mfma_kernel's fp64 far field, the
+// near field and SampleZ on the VALU.  A panel is decided as PB / 16 sub-panels of 16
+// rows, top down, so that 16 running sums are live across the SampleZ calls: the far
+// sums of the sub-panel wait in the wave's LDS tile, and the lower sub-panel of a
+// 32-row panel first takes the upper one's 16 coefficients (its own lane's stores)
+// through the near-field columns RC.  Every decision is certified with
+// cert_dmu(Ca, Cb, z1, mu) at the running z1 = sum_{j>i} |z_j|; an uncovered one is
+// redone at the reference-order mean with the lane's centre (resolve_coord above).
+// dmu_scale = 1 (a test hook widens the bound, which stays a bound, to force that
+// path).  Whole waves only: a.n % 64 == 0, ldz % 4 == 0, Z 16-byte aligned.
+template <typename ZT, int PB>
+__global__ __launch_bounds__(256) void klein_targets_kernel(const KleinArgs a,
+                                                            const double* __restrict__ RP,
+                                                            const double* __restrict__ RC,
+                                                            const double* __restrict__ CP, int64_t ldc,
+                                                            double dmu_scale, ZT* __restrict__ Z) {
+    constexpr int NT = PB / 16, LDF = 65;
+    __shared__ double Fl[4][16 * LDF];
+    __shared__ double tab_lds[2 * (kErfTabLast + 1)];
+    const lds_cdptr etab_s = stage_etab(tab_lds, a.etab);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t p0 = ((int64_t)blockIdx.x * 4 + wave) * 64;
+    if (p0 >= a.n) return;
+    const int64_t p = p0 + lane;
+    uint32_t chain, step;
+    lane_counter(a, p, chain, step);
+    CoordStream rs;
+    rs.init(a.seed, step, chain);
+    const int d = a.d;
+    const size_t ldz = (size_t)a.ldz;
+    double lw = 0.0, eb = 0.0, tb = 0.0;
+    unsigned int flags = 0;
+    const int npan = (d + PB - 1) / PB;
+    double* F = Fl[wave];
+    const int kq = lane >> 4, nq = lane & 15;
+    const double* __restrict__ cpp = CP + p;
+    double acc[16];
+    double z1 = 0.0;
+    for (int pk = 0; pk < npan; ++pk) {
+        const int p_hi = d - pk * PB;
+        d4_t f[NT][4];
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) f[t][g] = (d4_t){0.0, 0.0, 0.0, 0.0};
+        if (pk > 0) {
+            // coefficients of rows >= p_hi were stored by this wave's lanes in earlier panels
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            const double* __restrict__ rbase = RP + (size_t)PB * PB * ((size_t)pk * (pk - 1) / 2);
+            const ZT* __restrict__ zbase = Z + p0 + (size_t)p_hi * ldz;
+            const size_t roff = (size_t)kq * PB + nq, zoff = (size_t)kq * ldz + 4 * nq;
+            const size_t rstep = 4 * PB, zstep = 4 * ldz;
+            double ra[4][NT];
+            ZQuad<ZT> zq[4];
+#pragma unroll
+            for (int st = 0; st < 4; ++st) {
+#pragma unroll
+                for (int t = 0; t < NT; ++t) ra[st][t] = rbase[roff + 16 * t];
+                zq[st].load(zbase + zoff);
+                rbase += rstep;
+                zbase += zstep;
+            }
+            auto consume = [&](int st) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const double bz = zq[st].get(g);
+#pragma unroll
+                    for (int t = 0; t < NT; ++t)
+                        f[t][g] = __builtin_amdgcn_mfma_f64_16x16x4f64(ra[st][t], bz, f[t][g], 0, 0, 0);
+                }
+            };
+            // K = d - p_hi is a multiple of PB (>= 16): every step of 16 columns is full
+            for (int j0 = p_hi; j0 + 16 < d; j0 += 16) {
+#pragma unroll
+                for (int st = 0; st < 4; ++st) {
+                    consume(st);
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) ra[st][t] = rbase[roff + 16 * t];
+                    zq[st].load(zbase + zoff);
+                    rbase += rstep;
+                    zbase += zstep;
+                }
+            }
+#pragma unroll
+            for (int st = 0; st < 4; ++st) consume(st);
+        }
+#pragma unroll
+        for (int t = NT - 1; t >= 0; --t) {
+            const int top = p_hi - 16 * (NT - 1 - t);  // the sub-panel's rows: [top - 16, top)
+            if (top <= 0) break;
+            // tile t of D (lane: rows kq + 4 reg, chains 4 nq + g) -> one chain per lane
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) F[(kq + 4 * reg) * LDF + 4 * nq + g] = f[t][g][reg];
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = F[r * LDF + lane];
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (t < NT - 1) {
+                // rows top - 16 + r take the sub-panel above: columns c = top .. top + 15,
+                // R[top - 16 + r][c] = RC[c][c - 1 - (top - 16 + r)]
+                for (int c = top; c < top + 16; ++c) {
+                    const double x = (double)Z[(size_t)c * ldz + p];
+                    const cdptr rc = cst(RC) + (size_t)c * (PB - 1) + (c - top);
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[r] = fma(rc[15 - r], x, acc[r]);
+                }
+            }
+            const int rows = top < 16 ? top : 16;
+            double cpl = cpp[(size_t)(top - 1) * ldc];
+            for (int s = 0; s < rows; ++s) {
+                const int i = top - 1 - s;
+                const double mu = (cpl - acc[15]) * cst(a.irii)[i];
+                const double cpi = cpl;
+                if (i > 0) cpl = cpp[(size_t)(i - 1) * ldc];  // the next coordinate's centre, in flight
+                double zi = decide_coord<false>(a, i, mu, rs, lw, flags, etab_s,
+                                                cert_dmu(cst(a.cert)[2 * i], cst(a.cert)[2 * i + 1], z1, mu) * dmu_scale,
+                                                eb, tb);
+                if (zi == kAmbiguous) zi = resolve_coord(a, i, cpi, Z + p, ldz, rs, flags);
+                z1 += fabs(zi);
+                store_z(Z, (size_t)i * ldz + p, zi, flags);
+                const cdptr rc = cst(RC) + (size_t)i * (PB - 1);
+#pragma unroll
+                for (int k = 0; k < 15; ++k) acc[k] = fma(rc[14 - k], zi, acc[k]);
+#pragma unroll
+                for (int k = 15; k >= 1; --k) acc[k] = acc[k - 1];
+                acc[0] = 0.0;
+            }
+        }
+    }
+    if (flags) atomicOr(a.flags, flags);
+}
+
 // ------------------------------------------------------------ log density
 // compute_log_density (klein.py:222-271) of given coefficient vectors, reference
 // arithmetic order: sum_i -0.5*((z_i-mu_i)/sigma_i)^2 - (0.5*log(2pi) + log sigma_i)
@@ -3820,6 +4015,31 @@ hipError_t nearest_plane(int d, int64_t n, int panel, const double* RP, const do
         LGS_ZT(zb, ZT, hipLaunchKernelGGL((nearest_plane_kernel<ZT, 16>), grid, dim3(256), 0, st, d, n, RP, RC, rii, CP, ldc, (ZT*)Z, ldz, flags));
     else
         LGS_ZT(zb, ZT, hipLaunchKernelGGL((nearest_plane_kernel<ZT, 32>), grid, dim3(256), 0, st, d, n, RP, RC, rii, CP, ldc, (ZT*)Z, ldz, flags));
+    return hipGetLastError();
+}
+
+hipError_t klein_targets(const KleinArgs& a, const double* R, const double* RP, const double* RC, int panel,
+                         bool exact, const double* CP, int64_t ldc, double dmu_scale, int zb, void* Z,
+                         hipStream_t st) {
+    if (a.n <= 0) return hipSuccess;
+    if (zb != 4 && zb != 8) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((a.n + 255) / 256));
+    if (exact) {
+        if (zb == 4)
+            hipLaunchKernelGGL(klein_targets_exact_kernel<int32_t>, grid, dim3(256), 0, st, a, R, CP, ldc, (int32_t*)Z);
+        else
+            hipLaunchKernelGGL(klein_targets_exact_kernel<int64_t>, grid, dim3(256), 0, st, a, R, CP, ldc, (int64_t*)Z);
+        return hipGetLastError();
+    }
+    if (a.n % 64 != 0 || a.ldz % 4 != 0 || ((uintptr_t)Z % 16) != 0) return hipErrorInvalidValue;
+    if (panel == 16 && zb == 4)
+        hipLaunchKernelGGL((klein_targets_kernel<int32_t, 16>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int32_t*)Z);
+    else if (panel == 16)
+        hipLaunchKernelGGL((klein_targets_kernel<int64_t, 16>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int64_t*)Z);
+    else if (zb == 4)
+        hipLaunchKernelGGL((klein_targets_kernel<int32_t, 32>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int32_t*)Z);
+    else
+        hipLaunchKernelGGL((klein_targets_kernel<int64_t, 32>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int64_t*)Z);
     return hipGetLastError();
 }
 

@@ -35,6 +35,7 @@ LGS_SAMPLEZ_TABLE = 0x20
 LGS_SAMPLEZ_DECISION = 0x40
 LGS_SAMPLEZ_LIBM = 0x80
 LGS_LOGW_BOUND = 0x400
+LGS_TARGETS_QFRAME = 0x800
 
 LGS_X_I32 = 0x100
 LGS_X_I64 = 0x200
@@ -51,6 +52,7 @@ LGS_CTX_NO_CU_SPLIT = 0x80
 
 KERNEL_KLEIN, KERNEL_BZ, KERNEL_ACCEPT, KERNEL_MOMENTS = 0, 1, 2, 3
 KERNEL_GRAM, KERNEL_SERIES, KERNEL_KLEIN_INIT = 4, 5, 6
+KERNEL_CPRIME = 7  # lgs_klein_targets: the c' = Q^T t stage (transposes + GEMM)
 LGS_COUNTER_RESOLVED = 0
 LGS_COUNTER_FALLBACK = 1
 LGS_COUNTER_ACCEPT_RESOLVED = 2
@@ -63,7 +65,7 @@ EXPORTS = ("lgs_version", "lgs_last_error", "lgs_create", "lgs_create_ex", "lgs_
            "lgs_set_basis", "lgs_klein", "lgs_imhk", "lgs_imhk_trace", "lgs_imhk_ex", "lgs_lattice_points", "lgs_log_density", "lgs_sample_z", "lgs_timing_enable",
            "lgs_timing_get", "lgs_device_info", "lgs_series_stats", "lgs_gram",
            "lgs_jump_distance", "lgs_marginal_tvd", "lgs_column_range", "lgs_histogram", "lgs_set_decoder", "lgs_nearest_plane",
-           "lgs_round_decode", "lgs_counter")
+           "lgs_round_decode", "lgs_counter", "lgs_klein_targets")
 
 
 class ImhkOutputs(ctypes.Structure):
@@ -147,6 +149,9 @@ def load_library(path: str = LIB_PATH):
     L.lgs_set_decoder.argtypes = [_vp, _vp, _vp]
     L.lgs_nearest_plane.argtypes = [_vp, _i64, _vp, _vp, _vp, ctypes.c_uint32]
     L.lgs_round_decode.argtypes = [_vp, _i64, _vp, _vp, _vp, ctypes.c_uint32]
+    if hasattr(L, "lgs_klein_targets"):  # (older A/B baselines lack it)
+        L.lgs_klein_targets.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, _i64, _vp, _vp, _vp, _vp,
+                                        ctypes.c_uint32]
     for name in EXPORTS:
         if name not in ("lgs_version", "lgs_last_error") and hasattr(L, name):
             getattr(L, name).restype = ctypes.c_int
@@ -402,6 +407,46 @@ class Context:
                     continue
                 raise
             return z.astype(np.int64, copy=False), v
+        raise AssertionError("unreachable")
+
+    # ---------------------------------------------------------------- per-sample centres
+    def klein_targets(self, seed, first, targets, z_out=None, v_out=None, cprime_out=None, flags=0):
+        """Raw lgs_klein_targets on caller buffers (numpy host or device tensors): one Klein
+        draw around each target, sample k on the counters of Klein sample first + k.
+        targets is (n, d), or (d, n) with LGS_COORD_MAJOR; with LGS_TARGETS_QFRAME it holds
+        c' = Q^T t already."""
+        if len(targets.shape) != 2 or targets.shape[0 if flags & LGS_COORD_MAJOR else 1] != self.d:
+            raise ValueError(f"targets must be (n, {self.d}), or ({self.d}, n) with LGS_COORD_MAJOR")
+        n = targets.shape[1] if flags & LGS_COORD_MAJOR else targets.shape[0]
+        zt = "int64" if flags & LGS_Z64 else "int32"
+        _check_bufs(flags, self.device, ((targets, "float64", "targets"), (z_out, zt, "z_out"),
+                                         (v_out, "float64", "v_out"), (cprime_out, "float64", "cprime_out")))
+        self._ck(self._L.lgs_klein_targets(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(n),
+                                           _ptr(targets), _ptr(z_out), _ptr(v_out), _ptr(cprime_out),
+                                           int(flags)))
+
+    def klein_targets_host(self, seed, first, targets, *, want_z=True, want_v=True, want_cprime=False,
+                           flags=0):
+        """Klein draws around host targets (n, d) into fresh host arrays {"z", "v", "cprime"};
+        int32 coefficients first, int64 on overflow (same draws: fixed counters)."""
+        if flags & (LGS_DEVICE_PTRS | LGS_COORD_MAJOR):
+            raise ValueError("klein_targets_host takes row-major host targets")
+        t = np.ascontiguousarray(targets, dtype=np.float64)
+        if t.ndim != 2 or t.shape[1] != self.d:
+            raise ValueError(f"targets must be (n, {self.d})")
+        n = t.shape[0]
+        for z64 in (bool(flags & LGS_Z64), True):
+            f = flags | (LGS_Z64 if z64 else 0)
+            z = np.empty((n, self.d), dtype=np.int64 if z64 else np.int32) if want_z else None
+            v = np.empty((n, self.d)) if want_v else None
+            cp = np.empty((n, self.d)) if want_cprime else None
+            try:
+                self.klein_targets(seed, first, t, z, v, cp, f)
+            except LgsError as e:
+                if e.code == LGS_ERR_OVERFLOW and not z64:
+                    continue
+                raise
+            return {"z": None if z is None else z.astype(np.int64, copy=False), "v": v, "cprime": cp}
         raise AssertionError("unreachable")
 
     # ---------------------------------------------------------------- diagnostics

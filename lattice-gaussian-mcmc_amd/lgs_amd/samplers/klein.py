@@ -85,6 +85,7 @@ class RefinedKleinSampler(DiscreteGaussianSampler):
         self._ctx.set_basis(self.R, self.center_transformed, self.lattice.basis, self.sigma,
                             precision, linear_probs=not self.use_log_space)
         self._uploaded_precision = precision
+        self._decoder_uploaded = False
 
     @property
     def context(self) -> _capi.Context:
@@ -124,6 +125,38 @@ class RefinedKleinSampler(DiscreteGaussianSampler):
         if num_samples == 1:
             return self.sample_single().reshape(1, -1)
         return self.parallel_sample_batch(num_samples)
+
+    def sample_around(self, targets, coefficients: bool = False):
+        """One lattice point near each target: sample k is a draw of D_{L,sigma,t_k}
+        (klein.py:181-220 with the centre of base.py taken per sample instead of per
+        sampler) -- GPV preimage batches, randomized decoding.  A (d,) target gives a
+        (d,) point, (n, d) targets give (n, d); with coefficients=True returns
+        (points, z).  The draws use the sampler's next n sample counters, so they
+        never share one with sample()."""
+        t = np.asarray(targets, dtype=np.float64)
+        single = t.ndim == 1
+        if single:
+            t = t[None, :]
+        if t.ndim != 2 or t.shape[1] != self.dimension:
+            raise ValueError(f"targets must be ({self.dimension},) or (n, {self.dimension}), got {np.shape(targets)}")
+        n = t.shape[0]
+        if n == 0:
+            z0 = np.zeros((0, self.dimension), dtype=int)
+            return (np.zeros((0, self.dimension)), z0) if coefficients else np.zeros((0, self.dimension))
+        if self._uploaded_precision != self.precision:
+            self._upload(self.precision)
+        if not self._decoder_uploaded:
+            self._ctx.set_decoder(Q=self.Q)
+            self._decoder_uploaded = True
+        first = self._next_sample
+        self._next_sample += n
+        r = self._ctx.klein_targets_host(self.seed, first, t, want_z=coefficients, want_v=True,
+                                         flags=self._flags())
+        v = r["v"][0] if single else r["v"]
+        if not coefficients:
+            return v
+        z = r["z"].astype(int)
+        return v, (z[0] if single else z)
 
     def adaptive_precision_sample(self, target_distance: Optional[float] = None) -> np.ndarray:
         """klein.py:273-302."""
