@@ -143,6 +143,7 @@ struct lgs_ctx {
     bool has_qz2 = false;
     uint64_t n_accept_resolved = 0, n_wl_mismatch = 0;
     uint64_t n_qskip = 0;  // (wave, panel) pairs decided by the q-panel skip
+    uint64_t n_decode_resolved = 0;  // lgs_klein_decode: targets whose winner the bounds did not decide
     uint64_t n_fallback = 0;      // Klein launches redone with a wider store / fp64 far field
     // 32-row-panel kernels: the certificate's bound on sum_j |z_j| of a sample (an
     // estimate from the basis, then twice the largest sum seen; a sample exceeding it
@@ -187,13 +188,16 @@ struct lgs_ctx {
     int zint = 2;  // internal coefficient store width (bytes): 16-bit, sticky 32-bit on overflow; LGS_ZINT=4 forces 32-bit
     // timing
     bool timing = false;
-    double t_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int64_t t_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double t_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t t_n[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     // diagnostics scratch (lgs_series_stats / lgs_gram / lgs_jump_distance / lgs_marginal_tvd)
     DevBuf dg_x, dg_y, dg_out, dg_a, dg_b, dg_c, dg_t;
     // decoding frame (lgs_set_decoder): Q of the QR and (B^{-1})^T, row-major d x d
     DevBuf DQ, DBIT;
     DevBuf CPT;  // lgs_klein_targets: the chunk's centres c' = Q^T t, coordinate-major, padded to whole waves
+    // lgs_klein_decode: per-lane distance and bound, winners' columns / draw index / distance,
+    // the winners' compact coordinate-major store
+    DevBuf DEC_D, DEC_E, DEC_WIN, DEC_BEST, DEC_D2, DEC_Z;
     bool has_q = false, has_binv = false;
     std::vector<Timer> pending;
     std::vector<hipEvent_t> pool;
@@ -477,6 +481,7 @@ int finish(lgs_ctx* c, const unsigned int* fw_known = nullptr, bool clear_all = 
     c->n_accept_resolved += fw[lgs::kFlagWordAcceptResolved];
     c->n_wl_mismatch += fw[lgs::kFlagWordWLMismatch];
     c->n_qskip += fw[lgs::kFlagWordQSkip];
+    c->n_decode_resolved += fw[lgs::kFlagWordDecodeResolved];
     bool any = false;
     for (int k = 1; k < lgs::kFlagWords; ++k) any |= fw[k] != 0;
     if (clear_all)
@@ -2067,7 +2072,7 @@ int lgs_timing_enable(lgs_ctx* c, int enable) {
         fold_timers(c);
     }
     c->timing = enable != 0;
-    for (int k = 0; k < 8; ++k) {
+    for (int k = 0; k < 9; ++k) {
         c->t_ms[k] = 0;
         c->t_n[k] = 0;
     }
@@ -2076,7 +2081,7 @@ int lgs_timing_enable(lgs_ctx* c, int enable) {
 
 int lgs_timing_get(lgs_ctx* c, int kernel, double* ms, int64_t* n) {
     if (!c) return fail(LGS_ERR_INVALID, "null context");
-    if (kernel < 0 || kernel > 7) return fail(LGS_ERR_INVALID, "kernel id 0..7");
+    if (kernel < 0 || kernel > 8) return fail(LGS_ERR_INVALID, "kernel id 0..8");
     if (!c->pending.empty()) {  // launches of an early-checked call may still be running
         int rc = check_ctx(c, false);
         if (rc) return rc;
@@ -2090,8 +2095,8 @@ int lgs_timing_get(lgs_ctx* c, int kernel, double* ms, int64_t* n) {
 
 int lgs_counter(lgs_ctx* c, int which, int reset, uint64_t* value) {
     if (!c) return fail(LGS_ERR_INVALID, "null context");
-    if (which < LGS_COUNTER_RESOLVED || which > LGS_COUNTER_KLEIN_CUS)
-        return fail(LGS_ERR_INVALID, "counter id 0..5");
+    if (which < LGS_COUNTER_RESOLVED || which > LGS_COUNTER_DECODE_RESOLVED)
+        return fail(LGS_ERR_INVALID, "counter id 0..6");
     if (which == LGS_COUNTER_KLEIN_CUS) {
         if (value) *value = (uint64_t)c->kstream_cus;
         return LGS_OK;
@@ -2100,6 +2105,7 @@ int lgs_counter(lgs_ctx* c, int which, int reset, uint64_t* value) {
                   : which == LGS_COUNTER_FALLBACK    ? c->n_fallback
                   : which == LGS_COUNTER_ACCEPT_RESOLVED ? c->n_accept_resolved
                   : which == LGS_COUNTER_WL_MISMATCH ? c->n_wl_mismatch
+                  : which == LGS_COUNTER_DECODE_RESOLVED ? c->n_decode_resolved
                                                      : c->n_qskip;
     if (value) *value = v;
     if (reset) v = 0;
@@ -2685,6 +2691,154 @@ int lgs_klein_targets(lgs_ctx* c, uint64_t seed, uint64_t first, int64_t n, cons
         if (v_out) {
             double* V = dev ? v_out + (size_t)off * d : c->V.as<double>();
             if ((rc = run_bz(c, Zp, ob, mp, m, V))) return rc;
+            if ((rc = settle_bz(c))) return rc;
+            if (!dev)
+                HIP_TRY(hipMemcpyAsync(v_out + (size_t)off * d, V, (size_t)m * d * 8, hipMemcpyDeviceToHost,
+                                       c->stream));
+        }
+        if ((rc = finish(c))) return rc;
+    }
+    return finish(c);
+}
+
+// The closest of K Klein draws per target.  Per chunk of max_proposals / K targets: the
+// centres once per target into CPT (timer 7, lgs_klein_targets' stage) with
+// ceil(lanes / K) columns, the padding columns zeroed; the draw of lanes p = t K + k,
+// padded to whole waves, with each lane's distance and bound (timer 0); the selection,
+// one wave per target, and the gather of the winners into the compact store and the
+// caller's layout (timer 8); B z of the m winners.  The n K x d store stays internal.
+int lgs_klein_decode(lgs_ctx* c, uint64_t seed, uint64_t first, int64_t n, int64_t n_draws,
+                     const double* targets, void* z_out, double* v_out, double* cprime_out,
+                     const lgs_decode_outputs* out, uint32_t flags) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (flags & ~(uint32_t)(LGS_DEVICE_PTRS | LGS_Z64 | LGS_COORD_MAJOR | LGS_EXACT_ORDER | LGS_TARGETS_QFRAME))
+        return fail(LGS_ERR_INVALID, "lgs_klein_decode: unsupported flag 0x%x", flags);
+    if (n < 0) return fail(LGS_ERR_INVALID, "n < 0");
+    if (n_draws < 1 || n_draws > c->max_props)
+        return fail(LGS_ERR_INVALID, "n_draws must be 1..max_proposals (%lld)", (long long)c->max_props);
+    if (n == 0) return LGS_OK;
+    if (!targets) return fail(LGS_ERR_INVALID, "null targets");
+    const bool dev = flags & LGS_DEVICE_PTRS, z64 = flags & LGS_Z64, cm = flags & LGS_COORD_MAJOR,
+               exact = flags & LGS_EXACT_ORDER, qframe = flags & LGS_TARGETS_QFRAME;
+    if (!qframe && (!c->has_q || c->DQ.bytes < (size_t)c->d * c->d * 8))
+        return fail(LGS_ERR_STATE, "targets in the lattice frame need Q (lgs_set_decoder)");
+    if (v_out && !c->has_B) return fail(LGS_ERR_STATE, "v_out requires B");
+    const lgs_decode_outputs none{};
+    const lgs_decode_outputs& o = out ? *out : none;
+    const int64_t d = c->d, K = n_draws;
+    const int ob = z64 ? 8 : 4;
+    if ((rc = reset_flags(c))) return rc;
+    const int64_t chunk = std::min<int64_t>(n, c->max_props / K);
+    const int64_t lanes_p = (chunk * K + 63) / 64 * 64;
+    const int64_t ldc = (lanes_p + K - 1) / K;  // >= chunk: the centre columns the lanes read
+    const int64_t ldw = (chunk + 63) / 64 * 64;
+    if ((rc = c->CPT.reserve((size_t)ldc * d * 8)) || (rc = c->Z.reserve((size_t)lanes_p * d * ob)) ||
+        (rc = c->DEC_D.reserve((size_t)lanes_p * 8)) || (rc = c->DEC_E.reserve((size_t)lanes_p * 8)) ||
+        (rc = c->DEC_WIN.reserve((size_t)chunk * 8)) || (rc = c->DEC_BEST.reserve((size_t)chunk * 8)) ||
+        (rc = c->DEC_D2.reserve((size_t)chunk * 8)) || (rc = c->DEC_Z.reserve((size_t)ldw * d * ob)))
+        return rc;
+    if (!qframe && ((rc = c->dg_x.reserve((size_t)chunk * d * 8)) || (rc = c->dg_y.reserve((size_t)chunk * d * 8))))
+        return rc;
+    if (!dev) {
+        if ((rc = c->stage_a.reserve((size_t)chunk * d * 8))) return rc;
+        if (cprime_out && (rc = c->stage_b.reserve((size_t)chunk * d * 8))) return rc;
+        if (v_out && (rc = c->V.reserve((size_t)chunk * d * 8))) return rc;
+    }
+    double dmu_scale = 1.0;
+    // test hook (as lgs_klein_targets): a scale s < 1 widens every certificate bound, and
+    // with it every distance bound, by 1 / s
+    if (const char* s = hook("LGS_TEST_Z1CAP_SCALE")) {
+        const double v = atof(s);
+        if (v > 0.0 && v < 1.0) dmu_scale = 1.0 / v;
+    }
+    // test hook: the select kernel's path of d > 8192 (coefficients read from the store)
+    const bool stage_ok = !hook("LGS_TEST_DECODE_NOSTAGE");
+    double* X = c->CPT.as<double>();
+    for (int64_t off = 0; off < n; off += chunk) {
+        const int64_t m = std::min<int64_t>(chunk, n - off);
+        const int64_t mp = (m * K + 63) / 64 * 64;
+        {
+            Scope s(c, 7);
+            if (ldc > m) HIP_TRY(hipMemset2DAsync(X + m, (size_t)ldc * 8, 0, (size_t)(ldc - m) * 8, (size_t)d, c->stream));
+            if (qframe && cm) {
+                HIP_TRY(hipMemcpy2DAsync(X, (size_t)ldc * 8, targets + off, (size_t)n * 8, (size_t)m * 8, (size_t)d,
+                                         kind_of(true, dev), c->stream));
+            } else {
+                const double* src;  // row-major m x d on the device
+                if (cm) {           // lattice frame, coordinate-major: T (d x m) for the GEMM
+                    HIP_TRY(hipMemcpy2DAsync(c->dg_x.p, (size_t)m * 8, targets + off, (size_t)n * 8, (size_t)m * 8,
+                                             (size_t)d, kind_of(true, dev), c->stream));
+                    src = nullptr;
+                } else {
+                    src = targets + (size_t)off * d;
+                    if (!dev) {
+                        HIP_TRY(hipMemcpyAsync(c->stage_a.p, src, (size_t)m * d * 8, hipMemcpyHostToDevice, c->stream));
+                        src = c->stage_a.as<double>();
+                    }
+                    if (!qframe) HIP_TRY(lgs::launch::to_coord_major(src, 8, m, (int)d, c->dg_x.p, 8, m, c->stream));
+                }
+                if (!qframe) {
+                    HIP_TRY(lgs::launch::gemm_f64(c->dg_x.as<double>(), m, c->DQ.as<double>(), (int)d, m,
+                                                  c->dg_y.as<double>(), c->stream));
+                    src = c->dg_y.as<double>();
+                }
+                HIP_TRY(lgs::launch::to_coord_major(src, 8, m, (int)d, X, 8, ldc, c->stream));
+            }
+        }
+        lgs::KleinArgs a = base_args(c, seed);
+        a.counter_mode = 0;
+        a.base = first + (uint64_t)off * (uint64_t)K;
+        a.n = mp;
+        a.ldz = mp;
+        void* Zp = c->Z.p;
+        const lgs::DecodeLanes dl{K, c->DEC_D.as<double>(), c->DEC_E.as<double>()};
+        {
+            Scope s(c, 0);
+            c->hist.Z = nullptr;  // (no int16 history: B z reads the compact store)
+            HIP_TRY(lgs::launch::klein_decode(a, c->R.as<double>(), c->RP.as<double>(), c->RC.as<double>(), c->panel,
+                                              exact, X, ldc, dmu_scale, ob, Zp, dl, c->stream));
+        }
+        int64_t* best = dev && o.best_draw ? o.best_draw + off : c->DEC_BEST.as<int64_t>();
+        double* dist2 = dev && o.dist2 ? o.dist2 + off : c->DEC_D2.as<double>();
+        void* Wp = c->DEC_Z.p;
+        {
+            Scope s(c, 8);
+            HIP_TRY(lgs::launch::decode_select((int)d, m, K, dl.D, dl.E, c->RT.as<double>(), X, ldc, Zp, ob, mp,
+                                               c->DEC_WIN.as<int64_t>(), best, dist2, c->flags.as<unsigned int>(),
+                                               c->stream, stage_ok));
+            void* zrow = nullptr;  // row-major winners: the caller's device buffer, or staged
+            if (z_out && !cm) zrow = dev ? (char*)z_out + (size_t)off * d * ob : c->stage_a.p;
+            HIP_TRY(lgs::launch::decode_gather((int)d, m, c->DEC_WIN.as<int64_t>(), Zp, ob, mp, Wp, ldw, zrow, d, 1,
+                                               c->stream));
+            if (z_out && cm)
+                HIP_TRY(hipMemcpy2DAsync((char*)z_out + (size_t)off * ob, (size_t)n * ob, Wp, (size_t)ldw * ob,
+                                         (size_t)m * ob, (size_t)d, kind_of(dev, true), c->stream));
+            else if (z_out && !dev)
+                HIP_TRY(hipMemcpyAsync((char*)z_out + (size_t)off * d * ob, zrow, (size_t)m * d * ob,
+                                       hipMemcpyDeviceToHost, c->stream));
+        }
+        if (!dev) {
+            if (o.best_draw)
+                HIP_TRY(hipMemcpyAsync(o.best_draw + off, best, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
+            if (o.dist2) HIP_TRY(hipMemcpyAsync(o.dist2 + off, dist2, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
+        }
+        if (o.dist2_draws)
+            HIP_TRY(hipMemcpyAsync(o.dist2_draws + (size_t)off * K, dl.D, (size_t)m * K * 8, kind_of(dev, true),
+                                   c->stream));
+        if (o.bound_draws)
+            HIP_TRY(hipMemcpyAsync(o.bound_draws + (size_t)off * K, dl.E, (size_t)m * K * 8, kind_of(dev, true),
+                                   c->stream));
+        if (cprime_out) {  // row-major, the centres the kernel read
+            void* dst = dev ? (void*)(cprime_out + (size_t)off * d) : c->stage_b.p;
+            HIP_TRY(lgs::launch::transpose_out(X, 8, ldc, m, (int)d, dst, 8, c->stream));
+            if (!dev)
+                HIP_TRY(hipMemcpyAsync(cprime_out + (size_t)off * d, dst, (size_t)m * d * 8, hipMemcpyDeviceToHost,
+                                       c->stream));
+        }
+        if (v_out) {
+            double* V = dev ? v_out + (size_t)off * d : c->V.as<double>();
+            if ((rc = run_bz(c, Wp, ob, ldw, m, V))) return rc;
             if ((rc = settle_bz(c))) return rc;
             if (!dev)
                 HIP_TRY(hipMemcpyAsync(v_out + (size_t)off * d, V, (size_t)m * d * 8, hipMemcpyDeviceToHost,

@@ -195,7 +195,17 @@ struct KleinArgs {
 constexpr int kFlagWordAcceptResolved = 6;  // decisions redone at reference-order weights
 constexpr int kFlagWordWLMismatch = 7;      // recomputed draws that did not reproduce the stored z (a bug)
 constexpr int kFlagWordQSkip = 8;           // (wave, panel) pairs of the q-panel skip (klein_mfma_kernel)
+constexpr int kFlagWordDecodeResolved = 9;  // lgs_klein_decode: targets whose winner the bounds did not decide
 constexpr int kFlagWords = 16;              // the flag buffer: 64 bytes
+
+// Per-lane outputs of the decode sampling kernels (lgs_klein_decode): K draws per
+// target, lane p = t K + k; D[p] the draw's squared distance to its target as the kernel
+// formed it, E[p] >= |D[p] - reference-order distance|.
+struct DecodeLanes {
+    int64_t K;
+    double* D;
+    double* E;
+};
 
 struct AcceptArgs {
     int64_t nc;
@@ -398,6 +408,33 @@ hipError_t nearest_plane(int d, int64_t n, int panel, const double* RP, const do
 hipError_t klein_targets(const KleinArgs& a, const double* R, const double* RP, const double* RC, int panel,
                          bool exact, const double* CP, int64_t ldc, double dmu_scale, int zb, void* Z,
                          hipStream_t st);
+// lgs_klein_decode: K draws per target, lane p = t K + k.  klein_decode is klein_targets
+// with the centre of lane p in column p / K of CP (ceil(a.n / K) columns readable) and two
+// per-lane outputs: D[p], the kernel's own squared distance ||t - B z||^2 of the draw, and
+// E[p] >= |D[p] - D_ref[p]|, a rigorous bound against the reference-order distance (0 with
+// exact, where D is that distance).
+hipError_t klein_decode(const KleinArgs& a, const double* R, const double* RP, const double* RC, int panel,
+                        bool exact, const double* CP, int64_t ldc, double dmu_scale, int zb, void* Z,
+                        const DecodeLanes& dl, hipStream_t st);
+// Per target t < m: the draw of columns t K .. t K + K - 1 with the smallest
+// reference-order distance, ties to the smallest k.  Candidates are the draws whose interval
+// [D - E, D + E] reaches below min_k (D_k + E_k); a single candidate wins, several are
+// compared at their reference-order distance (RT = R transposed, row-major d x d; Z
+// coordinate-major, ld ldz; CP as above).  win[t] = the winner's column, best[t] = its k,
+// dist2[t] = its reference-order distance (always recomputed); *resolved counts the targets
+// that needed more than one such evaluation; a non-finite distance sets kFlagNonFinite.
+// d <= 4032: a workgroup per target, the draw's coefficients staged in LDS and the rows
+// shared by up to 16 waves; larger d, or stage_ok = false: a wave per target reading the
+// store.
+hipError_t decode_select(int d, int64_t m, int64_t K, const double* D, const double* E, const double* RT,
+                         const double* CP, int64_t ldc, const void* Z, int zb, int64_t ldz, int64_t* win,
+                         int64_t* best, double* dist2, unsigned int* flags, hipStream_t st,
+                         bool stage_ok = true);
+// Winners' columns of Z into the compact coordinate-major store W (ld ldw >= m; columns
+// m .. ldw - 1 zeroed) and, if out != nullptr, into out[t * st_t + i * st_i] (the
+// caller's layout), both of width zb.
+hipError_t decode_gather(int d, int64_t m, const int64_t* win, const void* Z, int zb, int64_t ldz, void* W,
+                         int64_t ldw, void* out, int64_t st_t, int64_t st_i, hipStream_t st);
 hipError_t round_coeffs(const double* W, int64_t ldw, int d, int64_t n, int zb, void* Z, int64_t ldz,
                         unsigned int* flags, hipStream_t st);
 hipError_t check_range16(const void* zs, int ob, int64_t count, unsigned int* flags, hipStream_t st);

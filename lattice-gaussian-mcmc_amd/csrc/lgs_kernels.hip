@@ -2248,15 +2248,22 @@ __device__ __forceinline__ double resolve_coord(const KleinArgs& a, int i, doubl
 
 // klein_exact_kernel with a per-lane centre: sequential j-ascending unfused sums
 // (klein.py:191-193).  Every lane of [0, a.n) is drawn: the caller pads CP and Z.
-template <typename ZT>
-__global__ __launch_bounds__(256) void klein_targets_exact_kernel(const KleinArgs a,
-                                                                  const double* __restrict__ R,
-                                                                  const double* __restrict__ CP, int64_t ldc,
-                                                                  ZT* __restrict__ Z) {
+//
+// DEC (lgs_klein_decode): K draws per target, lane p = t K + k reads the centre of
+// column p / K and also returns the squared distance of its draw to the target,
+// ||t - B z||^2 = sum_i r_i^2 with r_i = (c'_i - cs_i) - R_ii z_i (Q is square), see
+// DecodeLanes in lgs_kernels.h.  Here cs is the reference-order sum, so D is the
+// reference-order distance itself and the bound is 0.
+template <typename ZT, bool DEC>
+__device__ __forceinline__ void klein_targets_exact_body(const KleinArgs& a, const double* __restrict__ R,
+                                                         const double* __restrict__ CP, int64_t ldc,
+                                                         ZT* __restrict__ Z, const DecodeLanes& dl) {
     __shared__ double tab_lds[2 * (kErfTabLast + 1)];
     const lds_cdptr etab_s = stage_etab(tab_lds, a.etab);
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= a.n) return;
+    const double* __restrict__ cpp = CP + (DEC ? p / dl.K : p);
+    double D = 0.0;
     uint32_t chain, step;
     lane_counter(a, p, chain, step);
     CoordStream rs;
@@ -2267,14 +2274,40 @@ __global__ __launch_bounds__(256) void klein_targets_exact_kernel(const KleinArg
     unsigned int flags = 0;
     for (int i = d - 1; i >= 0; --i) {
         const double* __restrict__ Ri = R + (size_t)i * d;
-        const double cpl = CP[(size_t)i * ldc + p];
+        const double cpl = cpp[(size_t)i * ldc];
         double cs = 0.0;
         for (int j = i + 1; j < d; ++j) cs = cs + Ri[j] * (double)Z[(size_t)j * ldz + p];
         const double mu = (cpl - cs) / a.rii[i];
         const double zi = decide_coord<false>(a, i, mu, rs, lw, flags, etab_s, -1.0, eb, tb);
         store_z(Z, (size_t)i * ldz + p, zi, flags);
+        if (DEC) {
+            const double q = Ri[i] * zi;
+            const double r = (cpl - cs) - q;
+            D = D + r * r;
+        }
+    }
+    if (DEC) {
+        if (!isfinite(D)) flags |= kFlagNonFinite;
+        dl.D[p] = D;
+        dl.E[p] = 0.0;
     }
     if (flags) atomicOr(a.flags, flags);
+}
+
+template <typename ZT>
+__global__ __launch_bounds__(256) void klein_targets_exact_kernel(const KleinArgs a,
+                                                                  const double* __restrict__ R,
+                                                                  const double* __restrict__ CP, int64_t ldc,
+                                                                  ZT* __restrict__ Z) {
+    klein_targets_exact_body<ZT, false>(a, R, CP, ldc, Z, DecodeLanes{});
+}
+
+template <typename ZT>
+__global__ __launch_bounds__(256) void klein_decode_exact_kernel(const KleinArgs a,
+                                                                 const double* __restrict__ R,
+                                                                 const double* __restrict__ CP, int64_t ldc,
+                                                                 ZT* __restrict__ Z, const DecodeLanes dl) {
+    klein_targets_exact_body<ZT, true>(a, R, CP, ldc, Z, dl);
 }
 
 // Blocked, certified: the panel layout of klein_panel_kernel (RP / RC, PB = 16 or 32
@@ -2289,12 +2322,32 @@ __global__ __launch_bounds__(256) void klein_targets_exact_kernel(const KleinArg
 // redone at the reference-order mean with the lane's centre (resolve_coord above).
 // dmu_scale = 1 (a test hook widens the bound, which stays a bound, to force that
 // path).  Whole waves only: a.n % 64 == 0, ldz % 4 == 0, Z 16-byte aligned.
-template <typename ZT, int PB>
+//
+// DEC (lgs_klein_decode): the lane's centre is column p / K, and the lane accumulates
+// the distance Dt = sum_i rt_i^2 from what it already holds, rt_i = (c'_i - acc[15]) -
+// R_ii z_i, in the reference's order of i, with a rigorous bound E >= |Dt - D| on the
+// reference-order distance D.  With a = acc[15], s = the reference's cs:
+// |a - s| <= |R_ii| dmu_i (the certificate bounds exactly this difference, divided by
+// |R_ii|, before its 6e-16 |mu| term); the two subtractions round differently in the
+// two orders, the product R_ii z_i is the same number in both (same final z_i):
+//   |rt_i - r_i| <= e_i = 1.03 |R_ii| dmu_i + 2.4e-16 (|c'_i - a| + |rt_i|),
+//   |rt_i^2 - r_i^2| <= (2 |rt_i| + e_i) e_i =: A_i,
+// and both sums of d non-negative squares carry gamma_{d+1}:
+//   E = 1.01 sum A_i + 2.3e-16 (d + 2) Dt
+// (2 d u would do: the rest covers the select pass's roundings of Dt + E and Dt - E).
+// A decision redone in the reference order changes z_i, not how rt_i was formed.
+// The decode instantiation is klein_targets_kernel<ZT, PB, DecodeLanes> with the lanes'
+// outputs as a trailing argument; without it the kernel is lgs_klein_targets' own.
+__device__ __forceinline__ DecodeLanes decode_lanes() { return DecodeLanes{1, nullptr, nullptr}; }
+__device__ __forceinline__ DecodeLanes decode_lanes(const DecodeLanes& dl) { return dl; }
+
+template <typename ZT, int PB, typename... DL>
 __global__ __launch_bounds__(256) void klein_targets_kernel(const KleinArgs a,
                                                             const double* __restrict__ RP,
                                                             const double* __restrict__ RC,
                                                             const double* __restrict__ CP, int64_t ldc,
-                                                            double dmu_scale, ZT* __restrict__ Z) {
+                                                            double dmu_scale, ZT* __restrict__ Z, const DL... dls) {
+    constexpr bool DEC = sizeof...(DL) != 0;
     constexpr int NT = PB / 16, LDF = 65;
     __shared__ double Fl[4][16 * LDF];
     __shared__ double tab_lds[2 * (kErfTabLast + 1)];
@@ -2314,9 +2367,11 @@ __global__ __launch_bounds__(256) void klein_targets_kernel(const KleinArgs a,
     const int npan = (d + PB - 1) / PB;
     double* F = Fl[wave];
     const int kq = lane >> 4, nq = lane & 15;
-    const double* __restrict__ cpp = CP + p;
+    const DecodeLanes dl = decode_lanes(dls...);
+    const double* __restrict__ cpp = CP + (DEC ? p / dl.K : p);
     double acc[16];
     double z1 = 0.0;
+    double Dt = 0.0, At = 0.0;
     for (int pk = 0; pk < npan; ++pk) {
         const int p_hi = d - pk * PB;
         d4_t f[NT][4];
@@ -2398,12 +2453,23 @@ __global__ __launch_bounds__(256) void klein_targets_kernel(const KleinArgs a,
                 const double mu = (cpl - acc[15]) * cst(a.irii)[i];
                 const double cpi = cpl;
                 if (i > 0) cpl = cpp[(size_t)(i - 1) * ldc];  // the next coordinate's centre, in flight
+                double dmu = 0.0;
+                if constexpr (DEC) dmu = cert_dmu(cst(a.cert)[2 * i], cst(a.cert)[2 * i + 1], z1, mu) * dmu_scale;
                 double zi = decide_coord<false>(a, i, mu, rs, lw, flags, etab_s,
                                                 cert_dmu(cst(a.cert)[2 * i], cst(a.cert)[2 * i + 1], z1, mu) * dmu_scale,
                                                 eb, tb);
                 if (zi == kAmbiguous) zi = resolve_coord(a, i, cpi, Z + p, ldz, rs, flags);
                 z1 += fabs(zi);
                 store_z(Z, (size_t)i * ldz + p, zi, flags);
+                if constexpr (DEC) {
+                    const double xt = cpi - acc[15];
+                    const double rii = cst(a.rii)[i];
+                    const double q = rii * zi;
+                    const double rt = xt - q;
+                    Dt = Dt + rt * rt;
+                    const double e = 1.03 * (fabs(rii) * dmu) + 2.4e-16 * (fabs(xt) + fabs(rt));
+                    At += (2.0 * fabs(rt) + e) * e;
+                }
                 const cdptr rc = cst(RC) + (size_t)i * (PB - 1);
 #pragma unroll
                 for (int k = 0; k < 15; ++k) acc[k] = fma(rc[14 - k], zi, acc[k]);
@@ -2413,7 +2479,195 @@ __global__ __launch_bounds__(256) void klein_targets_kernel(const KleinArgs a,
             }
         }
     }
+    if constexpr (DEC) {
+        const double E = 1.01 * At + 2.3e-16 * (double)(d + 2) * Dt;
+        if (!isfinite(Dt) || !isfinite(E)) flags |= kFlagNonFinite;
+        dl.D[p] = Dt;
+        dl.E[p] = E;
+    }
     if (flags) atomicOr(a.flags, flags);
+}
+
+// ------------------------------------------------------------ decode: select + gather
+// Reference-order squared distance of one draw (column Zc of the store, centre column
+// cpc): D = sum over descending i of r_i^2, r_i = (c'_i - cs_i) - R_ii z_i, cs_i the
+// sequential j-ascending unfused sum of klein_targets_exact_kernel.  Rows are
+// independent, so a wave takes 64 rows at a time, one per lane with its own j loop
+// (RT: the lanes' R_ij are adjacent); decode_row_sq returns the lane's r_i^2 of row
+// top - lane (rows below 0: a value nobody adds).  STAGE: the draw's coefficients
+// come from an LDS copy zs (the store's columns are ldz apart: one cache line per
+// coefficient, read once instead of once per 64 rows).
+template <typename ZT, bool STAGE>
+__device__ __forceinline__ double decode_row_sq(int d, int top, const double* __restrict__ RT,
+                                                const double* __restrict__ cpc, int64_t ldc,
+                                                const ZT* __restrict__ Zc, size_t ldz, int lane,
+                                                const double* zs) {
+    const int lo = top >= 63 ? top - 63 : 0;  // the chunk's rows: lo .. top
+    const int i = top - lane;
+    const int ic = i >= lo ? i : lo;  // (idle lanes stay inside the buffers)
+    double cs = 0.0;
+#pragma unroll 8
+    for (int j = lo + 1; j < d; ++j) {
+        const double zj = STAGE ? zs[j] : (double)Zc[(size_t)j * ldz];
+        const double rij = RT[(size_t)j * d + ic];
+        cs = j > ic ? cs + rij * zj : cs;
+    }
+    const double q = RT[(size_t)ic * d + ic] * (STAGE ? zs[ic] : (double)Zc[(size_t)ic * ldz]);
+    const double r = (cpc[(size_t)ic * ldc] - cs) - q;
+    return r * r;
+}
+
+// The candidates of target t: U = min_k (D_k + E_k), the draws with D_k - E_k <= U
+// (the true winner is one of them); every wave that calls this gets the same answer.
+struct DecodeCand {
+    double U;
+    int64_t n, first;
+};
+__device__ __forceinline__ DecodeCand decode_candidates(const double* __restrict__ Dt,
+                                                        const double* __restrict__ Et, int64_t K, int lane) {
+    DecodeCand c{__builtin_inf(), 0, 0};
+    for (int64_t k = lane; k < K; k += 64) c.U = fmin(c.U, Dt[k] + Et[k]);
+    for (int o = 32; o; o >>= 1) c.U = fmin(c.U, __shfl_xor(c.U, o, 64));
+    for (int64_t k0 = 0; k0 < K; k0 += 64) {
+        const int64_t k = k0 + lane;
+        const unsigned long long mk = __builtin_amdgcn_ballot_w64(k < K && Dt[k] - Et[k] <= c.U);
+        if (mk && c.n == 0) c.first = k0 + __builtin_ctzll(mk);
+        c.n += __builtin_popcountll(mk);
+    }
+    return c;
+}
+
+// lgs_klein_decode's selection (launch::decode_select).  EVAL(kc) is the reference-order
+// distance of draw kc, the same value in every calling thread; one candidate wins
+// outright, several are compared in ascending k, and the winner's distance is always
+// evaluated.  Control flow is uniform over all threads that share a target.
+template <typename EVAL>
+__device__ __forceinline__ void decode_pick(const double* __restrict__ Dt, const double* __restrict__ Et,
+                                            int64_t K, int lane, EVAL eval, int64_t& kw, double& Dw,
+                                            unsigned int& nev) {
+    const DecodeCand c = decode_candidates(Dt, Et, K, lane);
+    kw = c.first;
+    nev = 1;
+    if (c.n <= 1) {
+        Dw = eval(kw);
+        return;
+    }
+    nev = 0;
+    Dw = 0.0;
+    for (int64_t k0 = 0; k0 < K; k0 += 64) {
+        const int64_t k = k0 + lane;
+        unsigned long long mk = __builtin_amdgcn_ballot_w64(k < K && Dt[k] - Et[k] <= c.U);
+        while (mk) {
+            const int64_t kc = k0 + __builtin_ctzll(mk);
+            mk &= mk - 1;
+            const double Dk = eval(kc);
+            if (nev == 0 || Dk < Dw) {  // ascending k: ties stay with the smallest
+                Dw = Dk;
+                kw = kc;
+            }
+            ++nev;
+        }
+    }
+}
+
+__device__ __forceinline__ void decode_write(int64_t t, int64_t K, int64_t kw, double Dw, unsigned int nev,
+                                             int64_t* __restrict__ win, int64_t* __restrict__ best,
+                                             double* __restrict__ dist2, unsigned int* flags) {
+    win[t] = t * K + kw;
+    best[t] = kw;
+    dist2[t] = Dw;
+    if (nev > 1) atomicAdd(flags + kFlagWordDecodeResolved, 1u);
+    if (!isfinite(Dw)) atomicOr(flags, kFlagNonFinite);
+}
+
+// One workgroup per target, blockDim.x / 64 <= 16 waves: an evaluation stages the draw's
+// d coefficients in LDS, the waves share its ceil(d / 64) chunks of rows (the j loops,
+// d^2 / 2 dependent additions in all, run 64 blockDim.x / 64 at a time), the squares
+// wait in LDS in descending i, and every wave adds them up in that order.  Dynamic
+// LDS: d + 64 ceil(d / 64) doubles.
+template <typename ZT>
+__global__ __launch_bounds__(1024) void decode_select_kernel(int d, int64_t K, const double* __restrict__ D,
+                                                             const double* __restrict__ E,
+                                                             const double* __restrict__ RT,
+                                                             const double* __restrict__ CP, int64_t ldc,
+                                                             const ZT* __restrict__ Z, int64_t ldz,
+                                                             int64_t* __restrict__ win, int64_t* __restrict__ best,
+                                                             double* __restrict__ dist2, unsigned int* flags) {
+    extern __shared__ double decode_lds[];
+    double* zs = decode_lds;
+    double* sqs = decode_lds + d;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int nch = (d + 63) / 64;
+    const int64_t t = blockIdx.x;
+    const double* __restrict__ cpc = CP + t;
+    const ZT* __restrict__ Zt = Z + t * K;
+    auto eval = [&](int64_t kc) -> double {
+        const ZT* __restrict__ Zc = Zt + kc;
+        __syncthreads();  // (the previous evaluation's reads)
+        for (int j = threadIdx.x; j < d; j += blockDim.x) zs[j] = (double)Zc[(size_t)j * ldz];
+        __syncthreads();
+        for (int c = wave; c < nch; c += nw)
+            sqs[c * 64 + lane] = decode_row_sq<ZT, true>(d, d - 1 - 64 * c, RT, cpc, ldc, Zc, (size_t)ldz, lane, zs);
+        __syncthreads();
+        double Ds = 0.0;  // sqs[x] is row d - 1 - x
+        for (int x = 0; x < d; ++x) Ds = Ds + sqs[x];
+        return Ds;
+    };
+    int64_t kw;
+    double Dw;
+    unsigned int nev;
+    decode_pick(D + t * K, E + t * K, K, lane, eval, kw, Dw, nev);
+    if (threadIdx.x == 0) decode_write(t, K, kw, Dw, nev, win, best, dist2, flags);
+}
+
+// One wave per target, no LDS (d beyond the workgroup kernel's LDS): the wave walks the
+// chunks of rows one after the other and adds each chunk's squares from its lanes.
+template <typename ZT>
+__global__ __launch_bounds__(256) void decode_select_wave_kernel(int d, int64_t m, int64_t K,
+                                                                 const double* __restrict__ D,
+                                                                 const double* __restrict__ E,
+                                                                 const double* __restrict__ RT,
+                                                                 const double* __restrict__ CP, int64_t ldc,
+                                                                 const ZT* __restrict__ Z, int64_t ldz,
+                                                                 int64_t* __restrict__ win,
+                                                                 int64_t* __restrict__ best,
+                                                                 double* __restrict__ dist2, unsigned int* flags) {
+    const int lane = threadIdx.x & 63;
+    const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= m) return;
+    const double* __restrict__ cpc = CP + t;
+    const ZT* __restrict__ Zt = Z + t * K;
+    auto eval = [&](int64_t kc) -> double {
+        double Ds = 0.0;
+        for (int top = d - 1; top >= 0; top -= 64) {
+            const double sq = decode_row_sq<ZT, false>(d, top, RT, cpc, ldc, Zt + kc, (size_t)ldz, lane, nullptr);
+            const int cnt = top >= 63 ? 64 : top + 1;
+            for (int l = 0; l < cnt; ++l) Ds = Ds + __shfl(sq, l, 64);
+        }
+        return Ds;
+    };
+    int64_t kw;
+    double Dw;
+    unsigned int nev;
+    decode_pick(D + t * K, E + t * K, K, lane, eval, kw, Dw, nev);
+    if (lane == 0) decode_write(t, K, kw, Dw, nev, win, best, dist2, flags);
+}
+
+// Winners into the compact store and the caller's layout (launch::decode_gather).
+template <typename ZT>
+__global__ __launch_bounds__(256) void decode_gather_kernel(int64_t m, const int64_t* __restrict__ win,
+                                                            const ZT* __restrict__ Z, int64_t ldz,
+                                                            ZT* __restrict__ W, int64_t ldw, ZT* __restrict__ out,
+                                                            int64_t st_t, int64_t st_i) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = blockIdx.y;
+    if (t >= ldw) return;
+    ZT v = 0;
+    if (t < m) {
+        v = Z[(size_t)i * ldz + win[t]];
+        if (out) out[t * st_t + i * st_i] = v;
+    }
+    W[(size_t)i * ldw + t] = v;
 }
 
 // ------------------------------------------------------------ log density
@@ -4040,6 +4294,74 @@ hipError_t klein_targets(const KleinArgs& a, const double* R, const double* RP, 
         hipLaunchKernelGGL((klein_targets_kernel<int32_t, 32>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int32_t*)Z);
     else
         hipLaunchKernelGGL((klein_targets_kernel<int64_t, 32>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int64_t*)Z);
+    return hipGetLastError();
+}
+
+hipError_t klein_decode(const KleinArgs& a, const double* R, const double* RP, const double* RC, int panel,
+                        bool exact, const double* CP, int64_t ldc, double dmu_scale, int zb, void* Z,
+                        const DecodeLanes& dl, hipStream_t st) {
+    if (a.n <= 0) return hipSuccess;
+    if ((zb != 4 && zb != 8) || dl.K < 1 || !dl.D || !dl.E) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((a.n + 255) / 256));
+    if (exact) {
+        if (zb == 4)
+            hipLaunchKernelGGL(klein_decode_exact_kernel<int32_t>, grid, dim3(256), 0, st, a, R, CP, ldc, (int32_t*)Z, dl);
+        else
+            hipLaunchKernelGGL(klein_decode_exact_kernel<int64_t>, grid, dim3(256), 0, st, a, R, CP, ldc, (int64_t*)Z, dl);
+        return hipGetLastError();
+    }
+    if (a.n % 64 != 0 || a.ldz % 4 != 0 || ((uintptr_t)Z % 16) != 0) return hipErrorInvalidValue;
+    if (panel == 16 && zb == 4)
+        hipLaunchKernelGGL((klein_targets_kernel<int32_t, 16, DecodeLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int32_t*)Z, dl);
+    else if (panel == 16)
+        hipLaunchKernelGGL((klein_targets_kernel<int64_t, 16, DecodeLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int64_t*)Z, dl);
+    else if (zb == 4)
+        hipLaunchKernelGGL((klein_targets_kernel<int32_t, 32, DecodeLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int32_t*)Z, dl);
+    else
+        hipLaunchKernelGGL((klein_targets_kernel<int64_t, 32, DecodeLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int64_t*)Z, dl);
+    return hipGetLastError();
+}
+
+hipError_t decode_select(int d, int64_t m, int64_t K, const double* D, const double* E, const double* RT,
+                         const double* CP, int64_t ldc, const void* Z, int zb, int64_t ldz, int64_t* win,
+                         int64_t* best, double* dist2, unsigned int* flags, hipStream_t st, bool stage_ok) {
+    if (m <= 0) return hipSuccess;
+    if ((zb != 4 && zb != 8) || K < 1) return hipErrorInvalidValue;
+    // a workgroup per target while its LDS (the draw's coefficients and the rows' squares)
+    // fits 64 KB, d <= 4032; beyond that a wave per target reading the store
+    const int nch = (d + 63) / 64;
+    const size_t lds = ((size_t)d + (size_t)nch * 64) * 8;
+    if (stage_ok && lds <= 65536) {
+        const dim3 grid((unsigned)m), block(64 * (nch < 16 ? nch : 16));
+        if (zb == 4)
+            hipLaunchKernelGGL(decode_select_kernel<int32_t>, grid, block, lds, st, d, K, D, E, RT, CP, ldc,
+                               (const int32_t*)Z, ldz, win, best, dist2, flags);
+        else
+            hipLaunchKernelGGL(decode_select_kernel<int64_t>, grid, block, lds, st, d, K, D, E, RT, CP, ldc,
+                               (const int64_t*)Z, ldz, win, best, dist2, flags);
+        return hipGetLastError();
+    }
+    const dim3 grid((unsigned)((m + 3) / 4));
+    if (zb == 4)
+        hipLaunchKernelGGL(decode_select_wave_kernel<int32_t>, grid, dim3(256), 0, st, d, m, K, D, E, RT, CP, ldc,
+                           (const int32_t*)Z, ldz, win, best, dist2, flags);
+    else
+        hipLaunchKernelGGL(decode_select_wave_kernel<int64_t>, grid, dim3(256), 0, st, d, m, K, D, E, RT, CP, ldc,
+                           (const int64_t*)Z, ldz, win, best, dist2, flags);
+    return hipGetLastError();
+}
+
+hipError_t decode_gather(int d, int64_t m, const int64_t* win, const void* Z, int zb, int64_t ldz, void* W,
+                         int64_t ldw, void* out, int64_t st_t, int64_t st_i, hipStream_t st) {
+    if (m <= 0) return hipSuccess;
+    if ((zb != 4 && zb != 8) || ldw < m) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((ldw + 255) / 256), (unsigned)d);
+    if (zb == 4)
+        hipLaunchKernelGGL(decode_gather_kernel<int32_t>, grid, dim3(256), 0, st, m, win, (const int32_t*)Z, ldz,
+                           (int32_t*)W, ldw, (int32_t*)out, st_t, st_i);
+    else
+        hipLaunchKernelGGL(decode_gather_kernel<int64_t>, grid, dim3(256), 0, st, m, win, (const int64_t*)Z, ldz,
+                           (int64_t*)W, ldw, (int64_t*)out, st_t, st_i);
     return hipGetLastError();
 }
 

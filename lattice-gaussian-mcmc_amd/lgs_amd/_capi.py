@@ -53,19 +53,21 @@ LGS_CTX_NO_CU_SPLIT = 0x80
 KERNEL_KLEIN, KERNEL_BZ, KERNEL_ACCEPT, KERNEL_MOMENTS = 0, 1, 2, 3
 KERNEL_GRAM, KERNEL_SERIES, KERNEL_KLEIN_INIT = 4, 5, 6
 KERNEL_CPRIME = 7  # lgs_klein_targets: the c' = Q^T t stage (transposes + GEMM)
+KERNEL_DECODE_SELECT = 8  # lgs_klein_decode: the select and gather launches
 LGS_COUNTER_RESOLVED = 0
 LGS_COUNTER_FALLBACK = 1
 LGS_COUNTER_ACCEPT_RESOLVED = 2
 LGS_COUNTER_WL_MISMATCH = 3
 LGS_COUNTER_QSKIP = 4
 LGS_COUNTER_KLEIN_CUS = 5
+LGS_COUNTER_DECODE_RESOLVED = 6
 
 # every symbol include/lgs.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = ("lgs_version", "lgs_last_error", "lgs_create", "lgs_create_ex", "lgs_destroy", "lgs_set_stream",
            "lgs_set_basis", "lgs_klein", "lgs_imhk", "lgs_imhk_trace", "lgs_imhk_ex", "lgs_lattice_points", "lgs_log_density", "lgs_sample_z", "lgs_timing_enable",
            "lgs_timing_get", "lgs_device_info", "lgs_series_stats", "lgs_gram",
            "lgs_jump_distance", "lgs_marginal_tvd", "lgs_column_range", "lgs_histogram", "lgs_set_decoder", "lgs_nearest_plane",
-           "lgs_round_decode", "lgs_counter", "lgs_klein_targets")
+           "lgs_round_decode", "lgs_counter", "lgs_klein_targets", "lgs_klein_decode")
 
 
 class ImhkOutputs(ctypes.Structure):
@@ -75,6 +77,12 @@ class ImhkOutputs(ctypes.Structure):
                 ("zk_index", ctypes.c_int64), ("fn_chains", ctypes.c_int64),
                 ("lag_L", ctypes.c_int64), ("lag_z_ring", ctypes.c_void_p), ("lag_z_sums", ctypes.c_void_p),
                 ("lag_v_ring", ctypes.c_void_p), ("lag_v_sums", ctypes.c_void_p), ("lag_v_scale", ctypes.c_double)]
+
+
+class DecodeOutputs(ctypes.Structure):
+    """struct lgs_decode_outputs (include/lgs.h)."""
+    _fields_ = [("best_draw", ctypes.c_void_p), ("dist2", ctypes.c_void_p),
+                ("dist2_draws", ctypes.c_void_p), ("bound_draws", ctypes.c_void_p)]
 
 
 class LgsError(RuntimeError):
@@ -152,6 +160,9 @@ def load_library(path: str = LIB_PATH):
     if hasattr(L, "lgs_klein_targets"):  # (older A/B baselines lack it)
         L.lgs_klein_targets.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, _i64, _vp, _vp, _vp, _vp,
                                         ctypes.c_uint32]
+    if hasattr(L, "lgs_klein_decode"):  # (older A/B baselines lack it)
+        L.lgs_klein_decode.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, _i64, _i64, _vp, _vp, _vp, _vp,
+                                       ctypes.POINTER(DecodeOutputs), ctypes.c_uint32]
     for name in EXPORTS:
         if name not in ("lgs_version", "lgs_last_error") and hasattr(L, name):
             getattr(L, name).restype = ctypes.c_int
@@ -447,6 +458,66 @@ class Context:
                     continue
                 raise
             return {"z": None if z is None else z.astype(np.int64, copy=False), "v": v, "cprime": cp}
+        raise AssertionError("unreachable")
+
+    # ---------------------------------------------------------------- decoding by sampling
+    def klein_decode(self, seed, first, targets, n_draws, z_out=None, v_out=None, cprime_out=None,
+                     best_draw=None, dist2=None, dist2_draws=None, bound_draws=None, flags=0):
+        """Raw lgs_klein_decode on caller buffers (numpy host or device tensors): the closest
+        of n_draws Klein draws around each target; draw k of target t is on the counters of
+        Klein sample first + t * n_draws + k.  targets as in klein_targets; best_draw (n,)
+        int64, dist2 (n,), dist2_draws / bound_draws (n, n_draws) float64, all optional."""
+        if len(targets.shape) != 2 or targets.shape[0 if flags & LGS_COORD_MAJOR else 1] != self.d:
+            raise ValueError(f"targets must be (n, {self.d}), or ({self.d}, n) with LGS_COORD_MAJOR")
+        n = targets.shape[1] if flags & LGS_COORD_MAJOR else targets.shape[0]
+        zt = "int64" if flags & LGS_Z64 else "int32"
+        _check_bufs(flags, self.device, ((targets, "float64", "targets"), (z_out, zt, "z_out"),
+                                         (v_out, "float64", "v_out"), (cprime_out, "float64", "cprime_out"),
+                                         (best_draw, "int64", "best_draw"), (dist2, "float64", "dist2"),
+                                         (dist2_draws, "float64", "dist2_draws"),
+                                         (bound_draws, "float64", "bound_draws")))
+        out = None
+        if not (best_draw is None and dist2 is None and dist2_draws is None and bound_draws is None):
+            out = DecodeOutputs(*(None if a is None else _ptr(a).value
+                                  for a in (best_draw, dist2, dist2_draws, bound_draws)))
+        self._ck(self._L.lgs_klein_decode(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(n),
+                                          int(n_draws), _ptr(targets), _ptr(z_out), _ptr(v_out),
+                                          _ptr(cprime_out), None if out is None else ctypes.byref(out),
+                                          int(flags)))
+
+    def klein_decode_host(self, seed, first, targets, n_draws, *, want_z=True, want_v=True, want_cprime=False,
+                          want_draws=False, flags=0):
+        """Decoding by sampling on host targets (n, d) into fresh host arrays {"z", "v",
+        "cprime", "best_draw", "dist2"} (and "dist2_draws", "bound_draws" with want_draws);
+        int32 coefficients first, int64 on overflow (same draws: fixed counters)."""
+        if flags & (LGS_DEVICE_PTRS | LGS_COORD_MAJOR):
+            raise ValueError("klein_decode_host takes row-major host targets")
+        t = np.ascontiguousarray(targets, dtype=np.float64)
+        if t.ndim != 2 or t.shape[1] != self.d:
+            raise ValueError(f"targets must be (n, {self.d})")
+        K = int(n_draws)
+        if K < 1:
+            raise ValueError("n_draws must be >= 1")
+        n = t.shape[0]
+        for z64 in (bool(flags & LGS_Z64), True):
+            f = flags | (LGS_Z64 if z64 else 0)
+            z = np.empty((n, self.d), dtype=np.int64 if z64 else np.int32) if want_z else None
+            v = np.empty((n, self.d)) if want_v else None
+            cp = np.empty((n, self.d)) if want_cprime else None
+            best, d2 = np.empty(n, dtype=np.int64), np.empty(n)
+            dd = np.empty((n, K)) if want_draws else None
+            bd = np.empty((n, K)) if want_draws else None
+            try:
+                self.klein_decode(seed, first, t, K, z, v, cp, best, d2, dd, bd, f)
+            except LgsError as e:
+                if e.code == LGS_ERR_OVERFLOW and not z64:
+                    continue
+                raise
+            r = {"z": None if z is None else z.astype(np.int64, copy=False), "v": v, "cprime": cp,
+                 "best_draw": best, "dist2": d2}
+            if want_draws:
+                r["dist2_draws"], r["bound_draws"] = dd, bd
+            return r
         raise AssertionError("unreachable")
 
     # ---------------------------------------------------------------- diagnostics

@@ -158,6 +158,40 @@ class RefinedKleinSampler(DiscreteGaussianSampler):
         z = r["z"].astype(int)
         return v, (z[0] if single else z)
 
+    def decode_around(self, targets, n_draws: int, coefficients: bool = False):
+        """Decoding by sampling (Klein 2000): for each target the closest of ``n_draws``
+        draws of D_{L,sigma,t} -- the draws ``sample_around`` would return for the target
+        repeated ``n_draws`` times, selected on the device (``lgs_klein_decode``: c' once
+        per target, only the winners leave the device).  A (d,) target gives a (d,)
+        point, (n, d) targets give (n, d); with coefficients=True returns (points, z).
+        Consumes the sampler's next n * n_draws sample counters."""
+        t = np.asarray(targets, dtype=np.float64)
+        single = t.ndim == 1
+        if single:
+            t = t[None, :]
+        if t.ndim != 2 or t.shape[1] != self.dimension:
+            raise ValueError(f"targets must be ({self.dimension},) or (n, {self.dimension}), got {np.shape(targets)}")
+        if isinstance(n_draws, bool) or not isinstance(n_draws, (int, np.integer)) or n_draws < 1:
+            raise ValueError(f"n_draws must be a positive integer, got {n_draws!r}")
+        n, K = t.shape[0], int(n_draws)
+        if n == 0:
+            z0 = np.zeros((0, self.dimension), dtype=int)
+            return (np.zeros((0, self.dimension)), z0) if coefficients else np.zeros((0, self.dimension))
+        if self._uploaded_precision != self.precision:
+            self._upload(self.precision)
+        if not self._decoder_uploaded:
+            self._ctx.set_decoder(Q=self.Q)
+            self._decoder_uploaded = True
+        first = self._next_sample
+        self._next_sample += n * K
+        r = self._ctx.klein_decode_host(self.seed, first, t, K, want_z=coefficients, want_v=True,
+                                        flags=self._flags())
+        v = r["v"][0] if single else r["v"]
+        if not coefficients:
+            return v
+        z = r["z"].astype(int)
+        return v, (z[0] if single else z)
+
     def adaptive_precision_sample(self, target_distance: Optional[float] = None) -> np.ndarray:
         """klein.py:273-302."""
         if target_distance is None:
