@@ -624,7 +624,6 @@ int run_klein(lgs_ctx* c, lgs::KleinArgs& a, bool exact, bool wl, int zb, void* 
         if (rc) return rc;
         if ((rc = c->ZNZ.reserve((size_t)blocks * lanes))) return rc;
         a.znz = c->ZNZ.as<uint8_t>();
-#ifndef LGS_NEAR_UNROLLED
         if (c->d % 16 == 0) {  // per-wave chunk bits for B z (zeroed: the kernel ORs into them)
             const int64_t words = (c->d + 2047) / 2048 * (lanes / 64);
             if ((rc = c->CLIVE.reserve((size_t)words * 4))) return rc;
@@ -632,7 +631,6 @@ int run_klein(lgs_ctx* c, lgs::KleinArgs& a, bool exact, bool wl, int zb, void* 
             a.clive = c->CLIVE.as<unsigned int>();
             a.clive_ld = lanes / 64;
         }
-#endif
         a.rd = c->RD.as<int8_t>();
         a.rd_off = c->RDOFF.as<int64_t>();
         a.h16 = c->H16.as<int16_t>();
@@ -1915,7 +1913,7 @@ static int imhk_impl(lgs_ctx* c, uint64_t seed, uint64_t first_chain, int64_t nc
         static const bool bz_f64 = hook_is("LGS_BZ_FP64", 1);
         const bool bz_mom = moments && v_samples && early && thin == 1 && kb == Tb && kb > 0 && zb == 2 &&
                             c->has_Bi8 && c->bz_mom_ok && !bz_f64 && c->hist.Z == c->Z.p && c->hist.Z &&
-                            c->hist.clive != nullptr && lgs::launch::bz_moments_supported() &&
+                            c->hist.clive != nullptr &&
                             d % 16 == 0 && d <= lgs::kOzMaxD && npb < ((int64_t)1 << 32) && !no_bz_mom;
         const bool fuse_final = !bz_mom && moments && !((z_samples || zk_samples) && kb > 0 && !carry) &&
                                 npb < ((int64_t)1 << 32);

@@ -14,32 +14,13 @@
 
 #include "lgs_kernels.h"
 
-// Round-5 near-field trims of klein_mfma_kernel, on by default (LGS_R5_OFF: the
-// round-4 forms, for A/B): the range checks and the sub-panel's nonzero flag from its
-// extremes and Z stored through the row's uniform base (LGS_TAIL2), the SampleZ
-// dispatch from the host's code in the record (LGS_DISP_CODE), the capped quantile
-// test without short-circuit branches (LGS_CAP_BRANCHLESS), each coordinate's int16
-// history value stored at once instead of packed through 8 registers
-// (LGS_HIST_STORE16), and the tail's integer extremes / running history pointer
-// (LGS_TAIL3).  Together 2.47 -> 2.32-2.37 ms per 2^18 C3 samples, identical outputs
+// Round-5 near-field trims of klein_mfma_kernel: the range checks and the sub-panel's
+// nonzero flag from its extremes and Z stored through the row's uniform base, the SampleZ
+// dispatch from the host's code in the record, the capped quantile test without
+// short-circuit branches, each coordinate's int16 history value stored at once instead
+// of packed through 8 registers, and the tail's integer extremes / running history
+// pointer.  Together 2.47 -> 2.32-2.37 ms per 2^18 C3 samples, identical outputs
 // (profiles/r05f_kb_trims.log, r05h_kb.log).
-#ifndef LGS_R5_OFF
-#ifndef LGS_TAIL2
-#define LGS_TAIL2 1
-#endif
-#ifndef LGS_DISP_CODE
-#define LGS_DISP_CODE 1
-#endif
-#ifndef LGS_CAP_BRANCHLESS
-#define LGS_CAP_BRANCHLESS 1
-#endif
-#ifndef LGS_HIST_STORE16
-#define LGS_HIST_STORE16 1
-#endif
-#ifndef LGS_TAIL3  // (integer extremes, running history pointer, the uncovered mask behind a ballot)
-#define LGS_TAIL3 1
-#endif
-#endif
 
 namespace lgs {
 
@@ -60,42 +41,19 @@ struct U4 {
 template <bool OPAQUE = true>  // false: keys may live in VGPRs (divergent callers)
 __device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                             uint32_t k0, uint32_t k1) {
-#ifndef LGS_PHILOX_HOIST
-    // opaque to loop-invariant motion: otherwise the 20 round keys of the (kernel-
-    // constant) seed are hoisted out of the coordinate loop, spilled to VGPR lanes
-    // and read back with v_readlane + s_nop at every call; recomputing them is 18 SALU
-    // adds.  (readfirstlane: the keys are the same in every lane, and the compiler may
-    // park them in a VGPR across a call)
-    if constexpr (OPAQUE) {
-        k0 = __builtin_amdgcn_readfirstlane(k0);
-        k1 = __builtin_amdgcn_readfirstlane(k1);
-        asm volatile("" : "+s"(k0), "+s"(k1));
-        // likewise the first round's products of the per-lane (step, chain) words:
-        // hoisted, they were spilled and reloaded from scratch at every draw
-        asm volatile("" : "+v"(c1), "+v"(c2));
-    }
-#endif
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         if (r) {
             k0 += 0x9E3779B9u;
             k1 += 0xBB67AE85u;
         }
-#ifdef LGS_PHILOX_MAD64
-        // one 32x32->64 multiply (v_mad_u64_u32) per product instead of mul_lo + mul_hi
-        // (round 4: the mul_lo / mul_hi pair below takes 13 fewer spilled VGPRs in the
-        // Klein kernel and runs it 2-4 % faster, profiles/r04ab_*, r04ac_*)
-        const uint64_t m0 = (uint64_t)0xD2511F53u * c0;
-        const uint64_t m1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t lo0 = (uint32_t)m0, hi0 = (uint32_t)(m0 >> 32);
-        const uint32_t lo1 = (uint32_t)m1, hi1 = (uint32_t)(m1 >> 32);
-#else
+        // a mul_lo / mul_hi pair per product, not one 32x32->64 multiply (v_mad_u64_u32):
+        // round 4, the pair takes 13 fewer spilled VGPRs in the Klein kernel and runs it
+        // 2-4 % faster (profiles/r04ab_*, r04ac_*)
         const uint32_t lo0 = 0xD2511F53u * c0;
         const uint32_t hi0 = __umulhi(0xD2511F53u, c0);
         const uint32_t lo1 = 0xCD9E8D57u * c2;
         const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2);
-#endif
-#ifndef LGS_PHILOX_NO_BITOP3
         if (OPAQUE && r >= 2) {
             // from the third round every word is per-lane: each three-way xor in one gfx950
             // v_bitop3_b32 (truth table 0x96) instead of two v_xor_b32 -- 16 VALU fewer per
@@ -109,7 +67,6 @@ __device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c
             c3 = lo0;
             continue;
         }
-#endif
         const uint32_t n0 = hi1 ^ c1 ^ k0;
         const uint32_t n2 = hi0 ^ c3 ^ k1;
         c0 = n0;
@@ -135,70 +92,16 @@ __device__ __forceinline__ double accept_uniform(uint64_t seed, uint32_t step, u
 template <bool OPAQUE = true>
 struct CoordStreamT {
     uint32_t k0, k1, step, chain;
-    uint32_t pair;  // cached pair index (0xffffffff = none); LGS_PHILOX2 (OPAQUE): cached quad index
+    uint32_t pair;  // cached pair index (0xffffffff = none)
     U4 w;
-#ifdef LGS_PHILOX2
-    U4 w2;  // the quad's second pair
-#endif
-#ifdef LGS_PHILOX_NEXT
-    U4 wn;          // the next pair's block, drawn at the current pair's second slot
-    uint32_t pn;    // its pair index (0xffffffff = none)
-#endif
     __device__ __forceinline__ void init(uint64_t seed, uint32_t step_, uint32_t chain_) {
         k0 = (uint32_t)seed;
         k1 = (uint32_t)(seed >> 32);
         step = step_;
         chain = chain_;
         pair = 0xffffffffu;
-#ifdef LGS_PHILOX_NEXT
-        pn = 0xffffffffu;
-#endif
     }
     __device__ __forceinline__ double u(uint32_t slot) {
-#ifdef LGS_DIAG_CHEAP_RNG  // diagnostic builds only: Philox cost probe (wrong stream)
-        uint32_t hh = (slot * 0x9E3779B9u) ^ (chain * 0x85EBCA6Bu) ^ step ^ k0;
-        hh ^= hh >> 15;
-        hh *= 0x2C1B3C6Du;
-        hh ^= hh >> 12;
-        return (double)hh * 0x1p-32;
-#endif
-#ifdef LGS_PHILOX2
-        // the Klein kernels' wave-uniform slots: the two Philox blocks of a quad of
-        // slots (4 coordinates) computed together -- two independent 10-round chains
-        // the scheduler interleaves -- behind a scalar test (the cache key is uniform)
-        if constexpr (OPAQUE) {
-            const uint32_t q = __builtin_amdgcn_readfirstlane(slot >> 2);
-            if (q != __builtin_amdgcn_readfirstlane(pair)) {
-                w = philox4x32_10<true>(2 * q, step, chain, kTagCoord, k0, k1);
-                w2 = philox4x32_10<true>(2 * q + 1, step, chain, kTagCoord, k0, k1);
-                pair = q;
-            }
-            const U4 ww = (slot & 2u) ? w2 : w;
-            return (slot & 1u) ? u53(ww.z, ww.w) : u53(ww.x, ww.y);
-        }
-#endif
-#ifdef LGS_PHILOX_NEXT
-        // software-pipelined (the Klein kernels' wave-uniform slots, ascending): the block
-        // of pair p + 1 is drawn at pair p's second slot, a step before its first use,
-        // off that step's decision chain; a slot sequence that jumps (skipped
-        // sub-panels) draws its block in place
-        if constexpr (OPAQUE) {
-            const uint32_t p = __builtin_amdgcn_readfirstlane(slot >> 1);
-            if (p != __builtin_amdgcn_readfirstlane(pair)) {
-                if (p == __builtin_amdgcn_readfirstlane(pn))
-                    w = wn;
-                else
-                    w = philox4x32_10<true>(p, step, chain, kTagCoord, k0, k1);
-                pair = p;
-            }
-            const double r = (slot & 1u) ? u53(w.z, w.w) : u53(w.x, w.y);
-            if (slot & 1u) {
-                wn = philox4x32_10<true>(p + 1, step, chain, kTagCoord, k0, k1);
-                pn = p + 1;
-            }
-            return r;
-        }
-#endif
         const uint32_t p = slot >> 1;
         if (p != pair) {
             w = philox4x32_10<OPAQUE>(p, step, chain, kTagCoord, k0, k1);
@@ -543,9 +446,8 @@ __device__ __forceinline__ ErfExp erf_gauss(double y, PolyErf) {
 
 // P(x) of the Euler-Maclaurin formula with NT Hermite correction terms
 // (NT = 6 for sigma < 50; 3 suffice above: the next term is < 1e-18 S).
-#define LGS_EM_ATTR __device__ __forceinline__
 template <int NT, typename TP>
-LGS_EM_ATTR double em_P_tab(double x, double mu, double sig, double is, TP etab, double& fx) {
+__device__ __forceinline__ double em_P_tab(double x, double mu, double sig, double is, TP etab, double& fx) {
     const double t = (x - mu) * is;
     const ErfExp ee = erf_gauss(t * kInvSqrt2, etab);
     fx = ee.g;
@@ -572,7 +474,7 @@ LGS_EM_ATTR double em_P_tab(double x, double mu, double sig, double is, TP etab,
 }
 
 template <typename TP>
-LGS_EM_ATTR double gauss_tab(double kd, double mu, double is, TP etab) {
+__device__ __forceinline__ double gauss_tab(double kd, double mu, double is, TP etab) {
     return erf_gauss((kd - mu) * is * kInvSqrt2, etab).g;
 }
 
@@ -623,14 +525,6 @@ __device__ __forceinline__ SampleZOut sample_z_em_tab(double mu, double sig, int
     return out;
 }
 
-// Not inlined: inlining lets the compiler hoist the ~100 polynomial constants of
-// erf/erfinv/exp/log out of the coordinate loop into registers (measured: 398
-// VGPR+AGPR, 1 wave/SIMD); as a call the kernel stays at <= 170 VGPRs.
-#ifndef LGS_SAMPLEZ_INLINE
-#define LGS_SAMPLEZ_ATTR __device__ __noinline__
-#else
-#define LGS_SAMPLEZ_ATTR __device__ __forceinline__
-#endif
 // Windows of at most 4 points (sigma < 0.1 gives at most 3): exponents first,
 // max-shift, and exp() only for the terms that do not underflow relative to the
 // largest (e - e_max < -745.2 gives exactly 0.0 in fp64, as exp would), so the
@@ -699,7 +593,10 @@ __device__ __forceinline__ bool sample_z_small(double mu, double sig, int precis
 }
 
 // etab == nullptr selects the libm Euler-Maclaurin path (ocml erf/exp/erfinv).
-LGS_SAMPLEZ_ATTR SampleZOut sample_z(double mu, double sig, int precision, bool linear_probs,
+// Not inlined (nor is sample_z_coord_leaf below): inlining lets the compiler hoist the ~100 polynomial constants of
+// erf/erfinv/exp/log out of the coordinate loop into registers (measured: 398
+// VGPR+AGPR, 1 wave/SIMD); as a call the kernel stays at <= 170 VGPRs.
+__device__ __noinline__ SampleZOut sample_z(double mu, double sig, int precision, bool linear_probs,
                                      double u, bool want_log, const double* __restrict__ etab,
                                      double dmu = -1.0) {
     if (sig < kEMMin) {
@@ -901,12 +798,6 @@ __device__ __constant__ double kCapCoef[36] = {
     -0.8188084361376584, 4.787814391235978, -17.187235185827564, 42.14891487326897, -68.64189227692192,
     71.76515059941498, -43.593212219926436, 11.853485934431038};
 constexpr int kCapE = 0, kCapG = 11, kCapRI = 23;
-// kCapCoef[kCapRI ..] as compile-time constants (LGS_CAP_IMM)
-constexpr double kCapRIImm[13] = {0.8862269447150851, 0.23200895985592382, 0.1278390124627034,
-                                  0.07920907048159789, 0.16780265291085433, -0.8188084361376584,
-                                  4.787814391235978, -17.187235185827564, 42.14891487326897,
-                                  -68.64189227692192, 71.76515059941498, -43.593212219926436,
-                                  11.853485934431038};
 __device__ __forceinline__ cdptr cap_coef() {
     cdptr p = (cdptr)kCapCoef;
     asm volatile("" : "+s"(p));
@@ -915,7 +806,7 @@ __device__ __forceinline__ cdptr cap_coef() {
 // Coefficients in SGPRs: Estrin's first level (both operands constants) costs a
 // VGPR copy per pair; a two-way Horner split (even and odd coefficients as two
 // interleaved Horner chains in x^2, each FMA with its scalar coefficient as the
-// addend) needs no copies at about half Horner's depth.  LGS_CAP_ESTRIN: Estrin.
+// addend) needs no copies at about half Horner's depth.
 template <int N>
 __device__ __forceinline__ double poly_h2(const double* c, double x);
 template <int N>
@@ -928,12 +819,6 @@ __device__ __forceinline__ double poly_estrin_p(cdptr cf, double x) {
 // the coefficients already in (scalar) registers
 template <int N>
 __device__ __forceinline__ double poly_h2(const double* c, double x) {
-#ifdef LGS_CAP_ESTRIN
-    double cc[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) cc[k] = c[k];
-    return poly_estrin(cc, x);
-#else
     // v_fma_f64 with the scalar coefficient as the addend, written out: left to
     // itself the compiler picks v_fmac_f64 and copies the coefficient into the
     // accumulator register first
@@ -950,7 +835,6 @@ __device__ __forceinline__ double poly_h2(const double* c, double x) {
 #pragma unroll
     for (int k = NO - 2; k >= 0; --k) po = fma_s(po, x2, c[2 * k + 1]);
     return fma(po, x, pe);
-#endif
 }
 
 // C(k) - base of a capped window with sigma >= 360 (Euler-Maclaurin with 3 terms,
@@ -1027,21 +911,6 @@ __device__ __noinline__ SzPair capped_slow(double c, double m, double sig, doubl
 #ifdef LGS_DIAG_CAPQ
 __device__ unsigned long long lgs_diag_capq[8];
 #endif
-// The erfinv coefficients kCapCoef[kCapRI..] loaded into scalar registers ahead of
-// the decision (load_cap_ri, at the top of a coordinate's step: the scalar-memory
-// round trip then overlaps the record reads instead of sitting on the chain).
-struct CapRI {
-    double c[13];
-};
-__device__ __forceinline__ CapRI load_cap_ri() {
-    const cdptr cf = cap_coef();
-    CapRI r;
-#pragma unroll
-    for (int k = 0; k < 13; ++k) r.c[k] = cf[kCapRI + k];
-#pragma unroll
-    for (int k = 0; k < 13; ++k) asm volatile("" : "+s"(r.c[k]));
-    return r;
-}
 // ln(x), x > 0 normal, with its constants through scalar registers (re-materialised
 // where used: ocml's log coefficients were hoisted out of the Wang-Ling Klein
 // near-field loop, spilled, and reloaded per coordinate behind vmcnt waits that also
@@ -1076,7 +945,7 @@ __device__ __forceinline__ double ln_fast(double x) {
 
 template <bool CERT, typename QP>
 __device__ __forceinline__ double sample_z_capped(double mu, double u, const QHead& h, QP q, bool want_log,
-                                                  double& log_norm, double dmu, const CapRI* ri = nullptr) {
+                                                  double& log_norm, double dmu) {
     const double sig = h.v[0], is = h.v[1];
     const double c = rint(mu);
     const double m = mu - c;
@@ -1091,24 +960,7 @@ __device__ __forceinline__ double sample_z_capped(double mu, double u, const QHe
     // continuous quantile x = m + sigma sqrt(2) erfinv(v): erfinv(v) = v R(v^2)
     const cdptr cf = cap_coef();
     const double v = fmin(fmax((target + base) * h.v[4], -0.8485), 0.8485);
-#ifdef LGS_CAP_IMM
-    // the erfinv coefficients as scalar immediates (s_mov) at the use: no scalar-memory
-    // round trip on the decision's dependency chain
-    CapRI rim;
-#pragma unroll
-    for (int k = 0; k < 13; ++k) {
-        rim.c[k] = kCapRIImm[k];
-        asm volatile("" : "+s"(rim.c[k]));
-    }
-    (void)cf;
-    const double xg = fma(h.v[5] * v, poly_h2<13>(rim.c, v * v), m);
-#else
-    const double xg = fma(h.v[5] * v, ri ? poly_h2<13>(ri->c, v * v) : poly_estrin_p<13>(cf + kCapRI, v * v), m);
-#endif
-#ifdef LGS_DIAG_CAP_GUESS  // diagnostic builds only (NOT bit-exact): cost probe, decision = the guess
-    return c + fmin(fmax(ceil(xg - 0.5), -500.0), 500.0);
-#endif
-#ifndef LGS_CAP_NO_QUANTILE
+    const double xg = fma(h.v[5] * v, poly_estrin_p<13>(cf + kCapRI, v * v), m);
     // Decision from the quantile alone, without evaluating C(k): with the window
     // sums C(k) of this kind (sigma >= 360), C(k) + base = sc erf(t(y_k) / sqrt 2)
     // at y_k = k + 1/2 + (k - m) / (24 sigma^2) to within 4e-11 units of y
@@ -1149,25 +1001,18 @@ __device__ __forceinline__ double sample_z_capped(double mu, double u, const QHe
             atomicMax(&lgs_diag_capq[7], (unsigned long long)(dmu * 1e15));
         }
 #endif
-#ifdef LGS_CAP_BRANCHLESS  // every condition evaluated: straight-line compares, no exec-masked branch
+        // every condition evaluated: straight-line compares, no exec-masked branch
         const bool fast = (xs - fl > tol) & (fl + 1.0 - xs > tol) & (fl >= -501.0) & (fl <= 499.0) &
                           (fabs(v) < 0.848) & (!CERT | (fabs(m) + 1.01 * dmu < 0.5));
-#else
-        const bool fast = xs - fl > tol && fl + 1.0 - xs > tol && fl >= -501.0 && fl <= 499.0 &&
-                          fabs(v) < 0.848 && (!CERT || fabs(m) + 1.01 * dmu < 0.5);
-#endif
         // a wave-uniform branch: the evaluation below must not be if-converted into
         // straight-line code that every wave runs
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(!fast) == 0, 1)) {
-#ifndef LGS_LN_OCML  // (Wang-Ling Klein 4.84 -> 4.11 ms per 2^18 C3 samples, profiles/r04ah_*)
+            // (ln_fast, not ocml's log: Wang-Ling Klein 4.84 -> 4.11 ms per 2^18 C3 samples,
+            // profiles/r04ah_*)
             log_norm = want_log ? ln_fast(S) : 0.0;
-#else
-            log_norm = want_log ? log(S) : 0.0;
-#endif
             return c + (fl + 1.0);
         }
     }
-#endif
     const SzPair r = capped_slow<CERT>(c, m, sig, is, S, base, target, xg, want_log, dmu);
     log_norm = r.ln;
     return r.z;
@@ -1294,17 +1139,15 @@ __device__ __forceinline__ double sample_z_coord_body(double mu, double u, QP qi
         return z;
     }
     if (kind == kSzGeneric) return __builtin_nan("");
-#ifndef LGS_NO_CAPPED_POLY
     if (kind == kSzCapped && qh.v[7] == 1.0)  // sigma >= 360 (host): series erf / exp
         return sample_z_capped<CERT>(mu, u, qh, q, want_log, log_norm, dmu);
-#endif
     return sig < 50.0
                ? sample_z_wide<6, CERT>(mu, u, qh, q, kind, precision, linear_probs, want_log, etab, log_norm, dmu)
                : sample_z_wide<3, CERT>(mu, u, qh, q, kind, precision, linear_probs, want_log, etab, log_norm, dmu);
 }
 
 template <bool CERT, typename TP, typename QP>
-LGS_SAMPLEZ_ATTR SzPair sample_z_coord_leaf(double mu, double u, QP q, int precision,
+__device__ __noinline__ SzPair sample_z_coord_leaf(double mu, double u, QP q, int precision,
                                             bool linear_probs, bool want_log, TP etab, double dmu) {
     SzPair r;
     r.ln = 0.0;
@@ -1344,14 +1187,9 @@ __device__ __forceinline__ double sample_z_coord(double mu, double u, QP q, int 
 }
 // The capped kind with sigma >= 360 alone (klein_mfma_kernel dispatches on the
 // kind itself): a small leaf, no kind dispatch inside (inlined into the rolled
-// near field, LGS_CAPPED_INLINE).
+// near field).
 template <bool CERT, typename QP>
-#ifdef LGS_CAPPED_INLINE
-__device__ __forceinline__
-#else
-__device__ __noinline__
-#endif
-SzPair sample_z_capped_leaf(double mu, double u, QP q, bool want_log, double dmu) {
+__device__ __forceinline__ SzPair sample_z_capped_leaf(double mu, double u, QP q, bool want_log, double dmu) {
     const QP qu = uniformize(q);
     const QHead qh = load_head(qu);
     SzPair r;

@@ -4,26 +4,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// Round-6 defaults of the Klein kernel's near field, measured together under the
-// scheduler flags (Makefile) with identical outputs: the record laid out decision-first
-// with its near-field coefficients read last (LGS_REC_L2), the record's LDS reads left
-// to the scheduler instead of pinned per register (LGS_REC_NOPIN), and the Philox round
-// keys left to loop-invariant motion (LGS_PHILOX_HOIST).  Each alone is within noise;
-// together the bench 117.0-117.4 -> 118.9-119.6 M samples/s and Klein 28.84-28.93 ->
-// 28.20-28.34 ms per 2^22 block (profiles/r06au_bench_variants.log), C3 / C4 / C5 Klein
-// -1.6 / -1.0 / -1.3 % at 2^20 samples and C1 / C2 +1.7 / +1.2 % (r06av_call_kbench.log).
-// LGS_R6_OFF restores the round-5 forms.
-#ifndef LGS_R6_OFF
-#ifndef LGS_REC_L2
-#define LGS_REC_L2 1
-#endif
-#ifndef LGS_REC_NOPIN
-#define LGS_REC_NOPIN 1
-#endif
-#ifndef LGS_PHILOX_HOIST
-#define LGS_PHILOX_HOIST 1
-#endif
-#endif
+// Compile-time switches (-D) the sources still read; everything else is fixed.  The
+// variants that were tried and removed are listed in DESIGN.md ("Variants tried and
+// removed").
+//   LGS_TEST_HOOKS    the hooks library: test and A/B switches read from the environment
+//                     (Makefile; the tests that perturb the certificate load it)
+//   LGS_NO_SPEC       no speculative sub-panels in klein_mfma_kernel
+//                     (tests/test_gpu_certificate.py, tools/gpu_spec_check.sh)
+//   LGS_OZ_DIGITS     R digits of the int8-digit far field, default 6 (tools/gpu_oz_digits.sh)
+//   LGS_DIAG_CYCLES   per-phase shader-clock counters of klein_mfma_kernel (tools/kbench.py)
+//   LGS_DIAG_FAR      per-wave shader-clock phases of the far field's chunk loop (tools/kbench.py)
+//   LGS_DIAG_CAPQ     why the capped kind's quantile decision falls through (tools/kbench.py)
 
 namespace lgs {
 
@@ -66,44 +57,37 @@ constexpr int kSzCb = kSzCa + 1;
 constexpr int kSzUsed = kSzCb + 1;  // 23
 constexpr int kSzcStride = 24;
 // Klein-path record per coordinate (kRecStride doubles): the SampleZ constants
-// [0, kSzUsed), then c', 1/R_ii, R_ii/sigma, 1/sigma_i^ref, lterm, and the 15
-// near-field coefficients R[i-1-m][i] of the coordinate's 16-row sub-panel.
-// Staged into LDS once per 32-row panel by klein_mfma_kernel.
-#ifdef LGS_REC_L2
-// (variant) the dispatch code and the weight constants before the near-field
+// [0, kSzUsed), then c', 1/R_ii, the dispatch code, R_ii/sigma, 1/sigma_i^ref, lterm,
+// CbC, and the 15 near-field coefficients R[i-1-m][i] of the coordinate's 16-row
+// sub-panel.  Staged into LDS once per 32-row panel by klein_mfma_kernel.
+// The dispatch code and the weight constants come before the near-field
 // coefficients: the step's decision then waits for the first 15 of the record's 22
-// 16-byte reads, and Rs[1..14] arrive while it runs
+// 16-byte reads, and Rs[1..14] arrive while it runs.  Round 6, measured together with
+// the record's LDS reads left to the scheduler (load_rec) and the Philox round keys left
+// to loop-invariant motion (philox4x32_10), identical outputs; each alone is within
+// noise, together the bench 117.0-117.4 -> 118.9-119.6 M samples/s and Klein 28.84-28.93
+// -> 28.20-28.34 ms per 2^22 block (profiles/r06au_bench_variants.log), C3 / C4 / C5
+// Klein -1.6 / -1.0 / -1.3 % at 2^20 samples and C1 / C2 +1.7 / +1.2 %
+// (r06av_call_kbench.log).
+//   kRecDisp   SampleZ dispatch code of the coordinate (host): 0.0 = small kind with one
+//              dominant window point possible (q[7] == 0), 1.0 = capped kind with
+//              sigma >= 360 (q[7] == 1), 2.0 = anything else (sigma_i == 0 included)
+//   kRecCbC    Cb of the certificate for a mean whose far field used only the 3 most
+//              significant R digits (reference mode, panels of two speculative
+//              sub-panels: klein_mfma_kernel)
 constexpr int kRecCp = kSzUsed, kRecIrii = kSzUsed + 1, kRecDisp = kSzUsed + 2, kRecRos = kSzUsed + 3,
               kRecIsr = kSzUsed + 4, kRecLterm = kSzUsed + 5, kRecCbC = kSzUsed + 6, kRecRs = kSzUsed + 7;
-constexpr int kRecScale = kRecRs + 15;
-constexpr int kRecSpec = kRecScale + 1;
-#else
-constexpr int kRecCp = kSzUsed, kRecIrii = kSzUsed + 1, kRecRos = kSzUsed + 2,
-              kRecIsr = kSzUsed + 3, kRecLterm = kSzUsed + 4, kRecRs = kSzUsed + 5;
-// SampleZ dispatch code of the coordinate (host): 0.0 = small kind with one dominant
-// window point possible (q[7] == 0), 1.0 = capped kind with sigma >= 360 (q[7] == 1),
-// 2.0 = anything else (sigma_i == 0 included); inside the hot record batch
-constexpr int kRecDisp = kRecRs + 15;
 // int8-digit far field (klein_mfma_kernel OZ): row scale 2^E_i of the
 // coordinate's row over its panel's far columns
-constexpr int kRecScale = kRecRs + 16;
-#endif
+constexpr int kRecScale = kRecRs + 15;
 // 1.0 when the coordinate's 16-row sub-panel is whole and all its coordinates are
 // of the small kind with one dominant window point possible (q[7] == 0): the
 // sub-panel is then decided speculatively in parallel (klein_mfma_kernel)
-#ifndef LGS_REC_L2
 constexpr int kRecSpec = kRecScale + 1;
-// Cb of the certificate for a mean whose far field used only the 3 most significant
-// R digits (reference mode, panels of two speculative sub-panels: klein_mfma_kernel)
-constexpr int kRecCbC = kRecScale + 2;
-#endif
 constexpr int kRecStride = 48;  // 384 bytes, 16-byte multiple
-#ifndef LGS_BZ_BN
-#define LGS_BZ_BN 128
-#endif
-// B z (bz_i8_kernel): coordinates per workgroup tile (128, or 64: half the
+// B z (bz_i8_kernel): coordinates per workgroup tile (64 was tried: half the
 // accumulators per wave, twice the workgroups)
-constexpr int kBzBN = LGS_BZ_BN;
+constexpr int kBzBN = 128;
 static_assert(kRecCbC < kRecStride, "record layout");
 constexpr int kOzCoarse = 4;  // R digits of the far field in coarse panels
 // int8-digit far field layout: per 32-row panel pk >= 1 (K = 32 pk far columns,
@@ -276,16 +260,6 @@ struct SeriesArgs {
 };
 
 namespace launch {
-// B z writes the kept states' moment partials (MP / MPL) on its clive path only: one
-// 64-sample tile per wave (LGS_BZ_TA == 1) and the Klein launch's per-wave chunk bits
-// (built by the rolled near field, not LGS_NEAR_UNROLLED; LGS_BZ_NO_CLIVE disables them)
-constexpr bool bz_moments_supported() {
-#if defined(LGS_BZ_NO_CLIVE) || defined(LGS_NEAR_UNROLLED) || (defined(LGS_BZ_TA) && LGS_BZ_TA != 1)
-    return false;
-#else
-    return true;
-#endif
-}
 // ---- diagnostics (lgs_diag.hip); xtype 0 fp64, 1 int32, 2 int64
 hipError_t series_stats(const SeriesArgs& a, hipStream_t st);
 // sum y y^T (d x d, both triangles) and sum y (d), y = x - shift (shift nullable),

@@ -21,11 +21,6 @@
 #include <type_traits>
 #include <stdint.h>
 
-// The rolled near field (default) decides the capped kind inline (one copy in the
-// loop body); the unrolled one (LGS_NEAR_UNROLLED) calls it as a leaf.
-#if !defined(LGS_NEAR_UNROLLED) && !defined(LGS_CAPPED_CALL) && !defined(LGS_CAPPED_INLINE)
-#define LGS_CAPPED_INLINE
-#endif
 #include "lgs_device.h"
 #include "lgs_kernels.h"
 
@@ -58,9 +53,6 @@ __device__ __forceinline__ double ref_weight(double zi, double mu, double ros, d
 // Certificate bound dmu >= |mu - mu_ref| of coordinate i (lgs_device.h "certified
 // decisions"; constants from lgs_set_basis), z1 = sum_{j>i} |z_j| of the sample.
 __device__ __forceinline__ double cert_dmu(double ca, double cb, double z1, double mu) {
-#ifdef LGS_DIAG_NO_CERT  // diagnostic builds only: cost probe of the certificate (NOT bit-exact)
-    return -1.0;
-#endif
     return fma(cb, z1, ca) + 6e-16 * fabs(mu);
 }
 
@@ -108,16 +100,6 @@ __device__ __forceinline__ double decide_coord(const KleinArgs& a, int i, double
         return 0.0;
     }
     const double s = a.szc ? cst(a.szc)[(size_t)i * kSzcStride] : cst(a.sig)[i];
-#ifdef LGS_DIAG_NO_SAMPLEZ
-    if (true) {  // diagnostic build: SampleZ replaced by rounding
-        zi = rint(mu + rs.u((uint32_t)(a.d - 1 - i)) * 1e-300);
-    } else
-#endif
-#ifdef LGS_DIAG_SZ_KIND_ONLY
-    if (a.szc && (int)cst(a.szc)[(size_t)i * kSzcStride + 2] != LGS_DIAG_SZ_KIND_ONLY) {
-        zi = rint(mu + rs.u((uint32_t)(a.d - 1 - i)) * 1e-300);
-    } else
-#endif
     if (s == 0.0) {  // sigma_i < 1e-10: round, no draw (klein.py:201-204)
         zi = rint(mu);
         if (dmu >= 0.0 && !round_stable(mu, dmu)) return kAmbiguous;
@@ -154,114 +136,26 @@ __device__ __forceinline__ double decide_coord(const KleinArgs& a, int i, double
 // coordinate's step, before anything branches on it: one LDS round trip per
 // coordinate instead of one per use site (mean, kind, window, polynomials,
 // weight terms, near-field coefficients), each behind the previous branch.
-// (LGS_CAP_RI_PRE: the capped kind's erfinv coefficients come along as scalar loads;
-// round 4: off by default -- without it, and with the Philox products as mul_lo /
-// mul_hi pairs, the kernel spills 49 instead of 63 VGPRs and runs C2 / C3 / C4 / C5
-// 4 / 2 / 3 / 3 % faster, outputs identical, profiles/r04ac_kbench_mulhi_noripre.log)
-#ifdef LGS_REC_L2
 constexpr int kRecHot = 46;  // (with the coarse panels' Cb, read in the batch instead of on its own)
-#else
-constexpr int kRecHot = 44;  // through the 15 near-field coefficients and the dispatch code
-#endif
 static_assert(kRecDisp < kRecHot && kRecRs + 15 <= kRecHot && kRecLterm < kRecHot, "hot record fields");
-#ifdef LGS_REC_SMEM
-// (experiment) the record read from the basis' record array in memory through a
-// wave-uniform constant pointer at each use: scalar loads into SGPRs (no LDS reads, no
-// 88 VGPRs holding wave-uniform values)
-struct RecRegs {
-    cdptr p;
-    __device__ __forceinline__ double operator[](int k) const { return p[k]; }
-};
-#elif defined(LGS_REC_RS_SMEM)
-// (experiment) the decision's fields from LDS as before, the 15 near-field coefficients
-// (used last in the step) through scalar loads
 struct RecRegs {
     double v[kRecHot];
-    cdptr p;
-    __device__ __forceinline__ double operator[](int k) const {
-        return (k >= kRecRs && k < kRecRs + 15) ? p[k] : v[k];
-    }
-};
-#else
-struct RecRegs {
-    double v[kRecHot];
-#ifdef LGS_CAP_RI_PRE
-    CapRI ri;
-#endif
     __device__ __forceinline__ double operator[](int k) const { return v[k]; }
 };
-#endif
-struct NoMid {
-    __device__ __forceinline__ void operator()() const {}
-};
-#ifdef LGS_REC_SMEM
-__device__ __forceinline__ RecRegs load_rec_g(cdptr grec) { return RecRegs{uniformize(grec)}; }
-#else
-template <typename MID = NoMid>
-#ifdef LGS_REC_RS_SMEM
-__device__ __forceinline__ RecRegs load_rec(lds_cdptr rec, cdptr gp, MID mid = MID{}) {
-#else
-__device__ __forceinline__ RecRegs load_rec(lds_cdptr rec, MID mid = MID{}) {
-#endif
+__device__ __forceinline__ RecRegs load_rec(lds_cdptr rec) {
     typedef double d2v __attribute__((ext_vector_type(2)));
     using lds_d2p = const __attribute__((address_space(3))) d2v*;
     RecRegs r;
-#ifdef LGS_REC_RS_SMEM
-    static_assert(kRecRs % 2 == 0 && kRecDisp == kRecRs + 15 && kRecHot == kRecDisp + 1, "record layout");
-#pragma unroll
-    for (int k = 0; k < kRecHot / 2; ++k) {
-        if (2 * k >= kRecRs && 2 * k + 1 < kRecRs + 15) continue;
-        const d2v t = ((lds_d2p)rec)[k];
-        r.v[2 * k] = t[0];
-        r.v[2 * k + 1] = t[1];
-    }
-    r.p = uniformize(gp);
-#else
 #pragma unroll
     for (int k = 0; k < kRecHot / 2; ++k) {
         const d2v t = ((lds_d2p)rec)[k];
         r.v[2 * k] = t[0];
         r.v[2 * k + 1] = t[1];
     }
-#endif
-    mid();
-#ifdef LGS_CAP_RI_PRE
-    r.ri = load_cap_ri();
-#endif
-    // pinned here: left alone, the compiler sinks each read into the branch that
-    // uses it (three round trips after the kind / window branches).
-#if !defined(LGS_REC_NOPIN) && !defined(LGS_REC_L2) && defined(LGS_REC_PIN_BATCH)
-    // (LGS_REC_PIN_BATCH: two asm statements over 22 registers each, one wait for the
-    // batch instead of one s_waitcnt lgkmcnt(k) per register -- the allocator then
-    // adds ~9 v_mov_b64 copies per step)
-    static_assert(kRecHot == 44, "two pins of 22");
-#define LGS_PIN22(o)                                                                                         \
-    asm volatile("" : "+v"(r.v[o + 0]), "+v"(r.v[o + 1]), "+v"(r.v[o + 2]), "+v"(r.v[o + 3]), "+v"(r.v[o + 4]),   \
-                 "+v"(r.v[o + 5]), "+v"(r.v[o + 6]), "+v"(r.v[o + 7]), "+v"(r.v[o + 8]), "+v"(r.v[o + 9]),        \
-                 "+v"(r.v[o + 10]), "+v"(r.v[o + 11]), "+v"(r.v[o + 12]), "+v"(r.v[o + 13]), "+v"(r.v[o + 14]),   \
-                 "+v"(r.v[o + 15]), "+v"(r.v[o + 16]), "+v"(r.v[o + 17]), "+v"(r.v[o + 18]), "+v"(r.v[o + 19]),   \
-                 "+v"(r.v[o + 20]), "+v"(r.v[o + 21]))
-    LGS_PIN22(0);
-    LGS_PIN22(22);
-#undef LGS_PIN22
-#elif !defined(LGS_REC_NOPIN)
-#pragma unroll
-    for (int k = 0; k < kRecHot; ++k)
-#ifdef LGS_REC_L2  // (Rs[1..14] not pinned: the first use waits for them)
-        if (k <= kRecRs)
-#elif defined(LGS_REC_RS_SMEM)
-        if (k < kRecRs || k >= kRecRs + 14)
-#endif
-            asm volatile("" : "+v"(r.v[k]));
-#endif
+    // the registers are not pinned: the scheduler places the reads, and the first use
+    // of Rs[1..14] waits for them
     return r;
 }
-#endif
-#ifdef LGS_REC_L2
-#define REC_CBC rr[kRecCbC]
-#else
-#define REC_CBC rec[kRecCbC]
-#endif
 struct RecView {  // q[k] of the SampleZ functions, served from the registers
     const RecRegs& r;
     __device__ __forceinline__ double operator[](int k) const { return r[k]; }
@@ -286,33 +180,6 @@ __device__ __forceinline__ double decide_coord_rec(const KleinArgs& a, int i, do
 #pragma unroll
     for (int k = 0; k < 9; ++k) qh.v[k] = rr[k];
     const double s = qh.v[0];
-#ifdef LGS_DIAG_NO_SAMPLEZ
-    if (true) {
-        zi = rint(mu + rs.u((uint32_t)(a.d - 1 - i)) * 1e-300);
-    } else
-#endif
-#ifdef LGS_DIAG_SZ_KIND_ONLY
-    if ((int)rec[2] != LGS_DIAG_SZ_KIND_ONLY) {
-        zi = rint(mu + rs.u((uint32_t)(a.d - 1 - i)) * 1e-300);
-    } else
-#endif
-#if defined(LGS_DISP_CODE) && defined(LGS_DISP_FIRST)
-    // the capped sigma >= 360 kind tested first, on the host's dispatch code (scalar),
-    // ahead of the sigma == 0 test (a vector compare and an exec-masked branch)
-    if (!LIBM && __builtin_amdgcn_readfirstlane(__double2hiint(rr[kRecDisp])) == 0x3ff00000) {
-        const double u = rs.u((uint32_t)(a.d - 1 - i));
-        SzPair r;
-        r.ln = 0.0;
-        r.z = sample_z_capped<CERT>(mu, u, qh, RecView{rr}, WL, r.ln, dmu);
-        double ln = 0.0;
-        zi = sz_finish<CERT>(r, mu, u, rec, a.precision, a.linear_probs != 0, WL, etab, ln, dmu, amb);
-        if (WL) {
-            lw += ln;
-            tb += fabs(ln);
-            eb += amb ? 0.0 : wl_bound_generic(ln, qh.v[1], wl_window_hw(qh.v[6]), dmu);
-        }
-    } else
-#endif
     // CERT: a decision not covered by the certificate is returned as a guess with
     // amb set and no weight term (the sub-panel's verification adds it); selects
     // instead of early returns keep the weight update branch-free (measured 13 vs
@@ -341,16 +208,10 @@ __device__ __forceinline__ double decide_coord_rec(const KleinArgs& a, int i, do
         double ln = 0.0;
         double ebf = 0.0;  // (WL) the fast decision's weight bound
         // the kind and its flag are the same in every lane: scalar branches
-#ifdef LGS_DISP_CODE
         // the host's dispatch code (kRecDisp): one scalar read of its high word (0 for
         // 0.0, 0x3ff00000 for 1.0) instead of converting the kind and testing q[7]
         const int dsp = __builtin_amdgcn_readfirstlane(__double2hiint(rr[kRecDisp]));
         const bool small_fast = dsp == 0, capped1 = dsp == 0x3ff00000;
-#else
-        const int kind = __builtin_amdgcn_readfirstlane((int)qh.v[2]);
-        const int q7 = __builtin_amdgcn_readfirstlane(qh.v[7] == 0.0 ? 0 : (qh.v[7] == 1.0 ? 1 : 2));
-        const bool small_fast = kind == kSzSmall && q7 == 0, capped1 = kind == kSzCapped && q7 == 1;
-#endif
         if (CERT && small_fast) {
             // the heaviest window point is rint(mu) (d1 = |mu - rint(mu)| < 1/2 unless a
             // tie, which fails the test); every other point lies >= 1 - d1 from mu, so
@@ -370,31 +231,12 @@ __device__ __forceinline__ double decide_coord_rec(const KleinArgs& a, int i, do
         if (!fast) {
             const double u = rs.u((uint32_t)(a.d - 1 - i));
             SzPair r;
-#ifdef LGS_DIAG_NO_GENERIC  // diagnostic builds only: cost of the generic call sites (NOT bit-exact)
-            if (capped1) {
-                r = sample_z_capped_leaf<CERT>(mu, u, rec, WL, dmu);
-                amb = CERT && (__builtin_isnan(r.z) || __builtin_isnan(r.ln));
-                zi = __builtin_isnan(r.z) ? rint(mu) : r.z;
-                ln = amb ? 0.0 : r.ln;
-            } else {
-                zi = rint(mu);
-            }
-            if (false)
-#endif
-            {
-#ifndef LGS_NO_CAPPED_POLY
             if (capped1) {  // sigma >= 360: the streamlined capped decision
                 r.ln = 0.0;
-#ifdef LGS_CAP_RI_PRE
-                r.z = sample_z_capped<CERT>(mu, u, qh, RecView{rr}, WL, r.ln, dmu, &rr.ri);
-#else
                 r.z = sample_z_capped<CERT>(mu, u, qh, RecView{rr}, WL, r.ln, dmu);
-#endif
             } else
-#endif
                 r = sample_z_coord_leaf<CERT>(mu, u, rec, a.precision, a.linear_probs != 0, WL, etab, dmu);
             zi = sz_finish<CERT>(r, mu, u, rec, a.precision, a.linear_probs != 0, WL, etab, ln, dmu, amb);
-            }
             if (WL) ebf = amb ? 0.0 : wl_bound_generic(ln, qh.v[1], wl_window_hw(qh.v[6]), dmu);
         }
         if (WL) {
@@ -416,15 +258,11 @@ __device__ __forceinline__ double decide_coord_rec(const KleinArgs& a, int i, do
 // the loop's back edge needs 15 v_mov_b64 per coordinate to shift the sums back.
 // The three-address v_fma_f64 writes acc[k + 1]'s own register: no moves, the same
 // fused operations (round 5: Klein 2.507 / 2.513 -> 2.443 / 2.456 ms per 2^18 C3
-// samples, identical outputs, profiles/r05b_kb.log).  LGS_NEAR_FMA_PLAIN: fma().
+// samples, identical outputs, profiles/r05b_kb.log).
 __device__ __forceinline__ double fma_shift(double a, double b, double c) {
-#ifndef LGS_NEAR_FMA_PLAIN
     double r;
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
-#else
-    return fma(a, b, c);
-#endif
 }
 
 // decide_coord_rec for a coordinate of a sub-panel the host flagged all capped with
@@ -976,9 +814,6 @@ __device__ unsigned long long lgs_diag_far[8];  // [0] history wait [1] slab sto
 #else
 #define LGS_DF_T(v)
 #endif
-#ifndef LGS_OZ_NG  // 16-sample groups per far-field pass (1 or 2)
-#define LGS_OZ_NG 2
-#endif
 
 __device__ __forceinline__ void oz_far_field(const KleinArgs& a, int pk, int p_hi, int64_t p0, int lane,
                                              lds_cdptr rec, double* F, int LDF, double (&acc)[16],
@@ -1010,179 +845,29 @@ __device__ __forceinline__ void oz_far_field(const KleinArgs& a, int pk, int p_h
     for (int g = 0; g < 4; ++g)
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) t0v[g][reg] = 0.0;
-#ifdef LGS_XP_ALIAS
-    // the upper row tile too: F shares its LDS with the slab, which later passes still use
-    double t1v[4][4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) t1v[g][reg] = 0.0;
-#endif
     // piece e of the slab is fragment e / 64 = (tile, digit) = ((e / 64) / kOzDigits, (e / 64) % kOzDigits);
     // a coarse panel's MFMAs read only the kOzCoarse most significant digits: the other
-    // pieces are neither loaded nor staged (LGS_OZ_COARSE_FULL_SLAB: staged, round 5)
+    // pieces are neither loaded nor staged
     auto piece_used = [&](int e) {
-#ifndef LGS_OZ_COARSE_FULL_SLAB
         return e < SLAB && (!coarse || (e >> 6) % kOzDigits < kOzCoarse);
-#else
-        return e < SLAB;
-#endif
     };
     auto slab_load = [&](int ch, v4i32_t (&pf)[4]) {
-#ifdef LGS_DIAG_FAR_NOSLAB
-        ch = 0;
-#endif
         const v4i32_t* src = rsrc + (size_t)ch * SLAB;
 #pragma unroll
         for (int m = 0; m < 4; ++m)
             if (piece_used(tid + 256 * m)) pf[m] = src[tid + 256 * m];
     };
     auto slab_store = [&](int buf, const v4i32_t (&pf)[4]) {
-#ifdef LGS_DIAG_FAR_NOSLAB  // diagnostic builds only (NOT bit-exact): no R-digit slab traffic (stale LDS)
-        asm volatile("" ::"v"(pf[0]));
-        return;
-#endif
 #pragma unroll
         for (int m = 0; m < 4; ++m)
             if (piece_used(tid + 256 * m)) ash4[buf * SLAB + tid + 256 * m] = pf[m];
     };
     // 4/NG passes of NG 16-sample groups: each A fragment read from LDS feeds 2 NG MFMAs
-    constexpr int NG = LGS_OZ_NG;
+    constexpr int NG = 2;  // 16-sample groups per far-field pass (1 or 2)
 #ifdef LGS_DIAG_FAR
     uint64_t df[8] = {};
     LGS_DF_T(tf_begin);
 #endif
-#ifdef LGS_OZ_PIPE_PASSES
-    // (round 6, measured and kept out: C3 7.90-8.07 vs 7.86-7.91 ms, C4 11.90-11.94 vs
-    // 11.79-11.81 ms per 2^20, profiles/r06g_kb.log) The passes as one pipelined sequence of (pass, live chunk) items:
-    // the loads of a pass's first chunk (history and R-digit slab) are issued during the
-    // previous pass's last chunk, as within a pass, instead of in a prologue of their
-    // own whose latency nothing hid; each pass's classes are recombined behind the
-    // barrier of its last chunk, while the next item's loads are in flight.
-    {
-        constexpr int NP = 4 / NG;
-        constexpr int NC = kOzDigits + 1;  // digit classes
-        v4i32_t cc[NG][2][NC];  // [group][row tile][class]
-        auto cc_zero = [&]() {
-#pragma unroll
-            for (int q = 0; q < NG; ++q)
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) cc[q][t][c] = (v4i32_t){0, 0, 0, 0};
-        };
-        cc_zero();
-        v4i32_t pf[4];
-        v4u_t w[NG][2];
-        auto hist_load = [&](int gp, int ch) {
-            const int16_t* __restrict__ hb0 = a.h16 + (blk0 * a.h16_lanes + p0 + 16 * NG * gp + n) * 16;
-            const v4u_t* h0 = (const v4u_t*)(hb0 + (size_t)ch * hstep);
-            w[0][0] = *(h0);
-            w[0][1] = *(h0 + 1);
-            if constexpr (NG == 2) {
-                const v4u_t* h1 = (const v4u_t*)(hb0 + 16 * 16 + (size_t)ch * hstep);  // group NG gp + 1
-                w[NG - 1][0] = *(h1);
-                w[NG - 1][1] = *(h1 + 1);
-            }
-        };
-        // classes -> fp64; D layout: rows 4h + reg of the tile, sample 16g + n
-        auto epilogue = [&](int gp) {
-#pragma unroll
-            for (int q = 0; q < NG; ++q)
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int reg = 0; reg < 4; ++reg) {
-                        const int g = NG * gp + q;
-                        const int row = 16 * t + 4 * h + reg;  // panel row = record index
-                        double sv = (double)cc[q][t][NC - 1][reg];
-#pragma unroll
-                        for (int c = NC - 2; c >= 0; --c) sv = fma(sv, 0.00390625, (double)cc[q][t][c][reg]);
-                        const double fv = sv * rec[row * kRecStride + kRecScale];
-                        if (t == 1) {
-#ifdef LGS_XP_ALIAS
-#pragma unroll
-                            for (int gg = 0; gg < 4; ++gg) t1v[gg][reg] = g == gg ? fv : t1v[gg][reg];
-#else
-                            F[(4 * h + reg) * LDF + 16 * g + n] = fv;
-#endif
-                        } else {
-#pragma unroll
-                            for (int gg = 0; gg < 4; ++gg) t0v[gg][reg] = g == gg ? fv : t0v[gg][reg];
-                        }
-                    }
-            cc_zero();
-        };
-        // (no barrier needed first: the panel's record-staging barrier also publishes nzm)
-        const int first = next_live(0);
-        if (first >= nch) {
-#pragma unroll 1
-            for (int gp = 0; gp < NP; ++gp) epilogue(gp);
-        } else {
-            // the item after (g, c): the next live chunk of pass g, else pass g + 1's first
-            auto advance = [&](int& g, int& c) {
-                c = next_live(c + 1);
-                if (c >= nch) {
-                    c = first;
-                    ++g;
-                }
-            };
-            int cgp = 0, cur = first;
-            int ngp = 0, nxt = first;
-            advance(ngp, nxt);
-            slab_load(cur, pf);
-            slab_store(0, pf);
-            if (ngp < NP) slab_load(nxt, pf);
-            hist_load(cgp, cur);
-            __syncthreads();
-#pragma unroll 1
-            for (int it = 0; cgp < NP; ++it) {
-                v4i32_t xh[NG], xl[NG];  // history of chunk cur -> digit planes, per group
-#pragma unroll
-                for (int q = 0; q < NG; ++q) {
-                    const v4u_t w0 = w[q][0], w1 = w[q][1];
-                    xh[q][0] = (int)__builtin_amdgcn_perm(w0[1], w0[0], 0x07050301u);
-                    xh[q][1] = (int)__builtin_amdgcn_perm(w0[3], w0[2], 0x07050301u);
-                    xh[q][2] = (int)__builtin_amdgcn_perm(w1[1], w1[0], 0x07050301u);
-                    xh[q][3] = (int)__builtin_amdgcn_perm(w1[3], w1[2], 0x07050301u);
-                    xl[q][0] = (int)(__builtin_amdgcn_perm(w0[1], w0[0], 0x06040200u) ^ 0x80808080u);
-                    xl[q][1] = (int)(__builtin_amdgcn_perm(w0[3], w0[2], 0x06040200u) ^ 0x80808080u);
-                    xl[q][2] = (int)(__builtin_amdgcn_perm(w1[1], w1[0], 0x06040200u) ^ 0x80808080u);
-                    xl[q][3] = (int)(__builtin_amdgcn_perm(w1[3], w1[2], 0x06040200u) ^ 0x80808080u);
-                }
-                int ngp2 = ngp, nxt2 = nxt;
-                if (ngp < NP) {  // the next item's history; its slab -> LDS, fetch the one after
-                    advance(ngp2, nxt2);
-                    hist_load(ngp, nxt);
-                    slab_store((it + 1) & 1, pf);
-                    if (ngp2 < NP) slab_load(nxt2, pf);
-                }
-                const v4i32_t* sl = ash4 + (it & 1) * SLAB + lane;
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int dg = 0; dg < kOzDigits; ++dg) {
-                        // coarse (wave-uniform): only the kOzCoarse most significant digits
-                        if (dg >= kOzCoarse && coarse) continue;
-                        const v4i32_t av = sl[(t * kOzDigits + dg) * 64];
-                        // digit a = dg + 1: class a - 1 with the high x digit, class a with the low
-#pragma unroll
-                        for (int q = 0; q < NG; ++q) {
-                            cc[q][t][dg] = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, xh[q], cc[q][t][dg], 0, 0, 0);
-                            cc[q][t][dg + 1] =
-                                __builtin_amdgcn_mfma_i32_16x16x64_i8(av, xl[q], cc[q][t][dg + 1], 0, 0, 0);
-                        }
-                    }
-                __syncthreads();  // next slab complete; this one's reads done before it is reused
-                if (ngp != cgp) epilogue(cgp);  // (the pass's last chunk)
-                cgp = ngp;
-                cur = nxt;
-                ngp = ngp2;
-                nxt = nxt2;
-            }
-        }
-    }
-#else
 #pragma unroll 1
     for (int gp = 0; gp < 4 / NG; ++gp) {
         constexpr int NC = kOzDigits + 1;  // digit classes
@@ -1198,9 +883,6 @@ __device__ __forceinline__ void oz_far_field(const KleinArgs& a, int pk, int p_h
         v4i32_t pf[4];
         v4u_t w[NG][2];
         auto hist_load = [&](int ch) {
-#ifdef LGS_DIAG_HIST_FIXED  // diagnostic builds only (NOT bit-exact): every chunk reads chunk 0's history
-            ch = 0;
-#endif
             const v4u_t* h0 = (const v4u_t*)(hb0 + (size_t)ch * hstep);
             const v4u_t* h1 = (const v4u_t*)(hb1 + (size_t)ch * hstep);
             w[0][0] = *(h0);
@@ -1212,9 +894,6 @@ __device__ __forceinline__ void oz_far_field(const KleinArgs& a, int pk, int p_h
                 (void)h1;
             }
         };
-#ifdef LGS_OZ_PASS_BARRIER
-        __syncthreads();  // previous pass done with both buffers
-#endif
         // (no barrier needed here: the previous pass's chunk loop ended with one after
         // its last slab reads, and pass 0 follows the panel's record-staging barrier,
         // which also publishes nzm)
@@ -1276,10 +955,6 @@ __device__ __forceinline__ void oz_far_field(const KleinArgs& a, int pk, int p_h
                     if (dg >= kOzCoarse && coarse) continue;
                     const v4i32_t av = sl[(t * kOzDigits + dg) * 64];
                     // digit a = dg + 1: class a - 1 with the high x digit, class a with the low
-#ifdef LGS_DIAG_FAR_NOMFMA  // diagnostic builds only (NOT bit-exact): the far field's loads and barriers alone
-                    asm volatile("" ::"v"(av), "v"(xh[NG - 1]), "v"(xl[NG - 1]));
-                    continue;
-#endif
 #pragma unroll
                     for (int q = 0; q < NG; ++q) {
                         cc[q][t][dg] = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, xh[q], cc[q][t][dg], 0, 0, 0);
@@ -1318,27 +993,13 @@ __device__ __forceinline__ void oz_far_field(const KleinArgs& a, int pk, int p_h
                     for (int c = NC - 2; c >= 0; --c) sv = fma(sv, 0.00390625, (double)cc[q][t][c][reg]);
                     const double fv = sv * rec[row * kRecStride + kRecScale];
                     if (t == 1) {
-#ifdef LGS_XP_ALIAS
-#pragma unroll
-                        for (int gg = 0; gg < 4; ++gg) t1v[gg][reg] = g == gg ? fv : t1v[gg][reg];
-#else
                         F[(4 * h + reg) * LDF + 16 * g + n] = fv;
-#endif
                     } else {
 #pragma unroll
                         for (int gg = 0; gg < 4; ++gg) t0v[gg][reg] = g == gg ? fv : t0v[gg][reg];
                     }
                 }
     }
-#endif
-#ifdef LGS_XP_ALIAS
-    // every pass's chunk loop ended with a block barrier after its last slab reads (and
-    // a block without live chunks never touched the slab): F is free for every wave
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) F[(4 * h + reg) * LDF + 16 * g + n] = t1v[g][reg];
-#endif
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -1361,12 +1022,6 @@ __device__ __forceinline__ void oz_far_field(const KleinArgs& a, int pk, int p_h
 #endif
 }
 
-#ifndef LGS_MFMA_LB32
-#define LGS_MFMA_LB32 3
-#endif
-#ifndef LGS_OZ_LB  // waves per SIMD the int8-digit far-field kernel is compiled for
-#define LGS_OZ_LB 2
-#endif
 // Diagnostic builds (-DLGS_DIAG_CYCLES): per-wave shader-clock accounting of the
 // 32-row-panel kernel, summed over waves into lgs_diag_cycles (lane 0 adds):
 // [0] record staging + barriers, [1] far field, [2] near field, [3 + kind] the
@@ -1380,44 +1035,30 @@ __device__ unsigned long long lgs_diag_cycles[16];
 #define LGS_DC_T(v)
 #define LGS_DC_ADD(k, x)
 #endif
+// waves per SIMD the 32-row-panel kernel is compiled for: the int8-digit far field
+// (OZ), the fp64 MFMA far field
+constexpr int kOzLB = 2, kMfmaLB32 = 3;
 // OZ (32-row panels only): far field as an exact int8-digit product on
 // v_mfma_i32_16x16x64_i8 instead of fp64 MFMA (see oz_far_field).
 template <typename ZT, int PB, bool WL, bool OZ = false, bool LIBM = false>
-__global__ __launch_bounds__(256, PB == 32 ? (OZ ? LGS_OZ_LB : LGS_MFMA_LB32) : 3) void klein_mfma_kernel(const KleinArgs a,
+__global__ __launch_bounds__(256, PB == 32 ? (OZ ? kOzLB : kMfmaLB32) : 3) void klein_mfma_kernel(const KleinArgs a,
                                                             const double* __restrict__ RP,
                                                             const double* __restrict__ RC,
                                                             ZT* __restrict__ Z) {
     if (a.gate && *a.gate == 0u) return;  // whole grid: nothing to draw
     constexpr int NT = PB / 16, LDF = 65;  // LDS tile pitch (doubles): conflict-free row reads
-#ifdef LGS_XP_ALIAS  // (experiment: the far-field tiles share the R-digit slab's LDS)
-    __shared__ __attribute__((aligned(16))) double Fl_raw[4 * 16 * LDF];
-    double (*Fl)[16 * LDF] = (double (*)[16 * LDF])Fl_raw;
-#else
     __shared__ double Fl[4][16 * LDF];
-#endif
     // OZ: the erf table stays in global memory (L1-resident lookups measured as fast
-    // as LDS) to leave LDS for the block-shared R-digit slab of the far field
+    // as LDS) to leave LDS for the block-shared R-digit slab of the far field (its
+    // Taylor-coefficient form, CoefTab, measured 2 % slower: load latency)
     __shared__ double tab_lds[OZ ? 2 : 2 * (kErfTabLast + 1)];
-#ifdef LGS_XP_ALIAS
-    int8_t* ash = (int8_t*)Fl_raw;
-#else
     __shared__ __attribute__((aligned(16))) int8_t ash[OZ ? 2 * 2 * kOzDigits * 1024 : 16];  // 2 x 14 KB
-#endif
-#ifdef LGS_COEF_ON  // Taylor-coefficient table: measured 2% slower (load latency)
-    using ETP = std::conditional_t<OZ, CoefTab, lds_cdptr>;
-    ETP etab_s;
-    if constexpr (OZ)
-        etab_s = CoefTab{a.etab2};
-    else
-        etab_s = stage_etab(tab_lds, a.etab);
-#else
     using ETP = std::conditional_t<OZ, gdptr, lds_cdptr>;
     ETP etab_s;
     if constexpr (OZ)
         etab_s = (gdptr)a.etab;
     else
         etab_s = stage_etab(tab_lds, a.etab);
-#endif
     // 32-row panels: the panel's per-coordinate records, staged block-wide
     __shared__ __attribute__((aligned(16))) double rec_lds[PB == 32 ? 32 * kRecStride : 2];
     // OZ: bit q set when panel q has a nonzero coefficient in some sample of the block
@@ -1452,29 +1093,15 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? LGS_OZ_LB : LGS_MFMA_LB32) : 
     // measured 0.7 ms slower per 2^20 samples): [0] the running sum of |z_j|, [1] it
     // and [2] the weight at the start of the current sub-panel (for a replay)
     __shared__ double cert_lds[3][PB == 32 ? 256 : 1];
-    // bit s: decision s of the current sub-panel not covered by the certificate (in
-    // LDS, written only when set: a live mask register costs ~13 scratch ops per
-    // coordinate at this kernel's register pressure)
-#ifdef LGS_NEAR_UNROLLED
-    __shared__ int cert_fl[PB == 32 ? 256 : 1];
-#endif
     // q-panel skip (reference mode, a.qz2): per lane sum z_j^2 over the coordinates
     // outside speculative sub-panels (+inf once a speculative coordinate is nonzero),
     // and the block's vote for skipping the current panel
     __shared__ double qzs[PB == 32 ? 256 : 1];
-#ifdef LGS_QSKIP_STAGED
-    __shared__ int qskip_blk[2];  // (by panel parity: a wave may start the next panel before another
-                                  // has read this panel's vote when there is no block barrier between)
-#else
     // each wave's vote, by panel parity (a wave reaches panel pk + 2 only after every wave
     // has passed panel pk + 1's barrier, i.e. read panel pk's votes)
     __shared__ int qvote[2][4];
-#endif
     if constexpr (PB == 32) {
         cert_lds[0][threadIdx.x] = 0.0;
-#ifdef LGS_NEAR_UNROLLED
-        cert_fl[threadIdx.x] = 0;
-#endif
         qzs[threadIdx.x] = 0.0;
     }
     for (int pk = 0; pk < npan; ++pk) {
@@ -1493,30 +1120,9 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? LGS_OZ_LB : LGS_MFMA_LB32) : 
             // blocked mean (isr and ros are R_ii / sigma in two roundings).  Block-wide
             // (the far field stages the R-digit slab with block barriers).
             bool qtry = false;
-#if !defined(LGS_NEAR_UNROLLED) && !defined(LGS_NO_QSKIP_CODE)  // (that variant does not track ||z_W||)
             if constexpr (OZ && !WL)
                 qtry = a.qz2 != nullptr && p_hi >= 32 && ((const __attribute__((address_space(4))) double*)a.qz2)[pk] >= 0.0;
-#endif
             const int r0 = p_hi - 32;
-#ifdef LGS_QSKIP_STAGED  // (round 5: the panel's records staged before the vote is read)
-            // records of coordinates r0 .. r0+31 (r0 = p_hi - 32; negative ones skipped)
-            if (qtry && threadIdx.x == 0) qskip_blk[pk & 1] = 1;  // (read last at panel pk - 2: done)
-            __syncthreads();
-            if (qtry) {
-                const double q2 = ((const __attribute__((address_space(4))) double*)a.qz2)[pk];
-                if (__builtin_amdgcn_ballot_w64(active && !(qzs[threadIdx.x] <= q2)) != 0 && lane == 0)
-                    qskip_blk[pk & 1] = 0;
-            }
-            bool skip = false;
-            {
-                const double2* __restrict__ src = (const double2*)a.crec;
-                double2* dst = (double2*)rec_lds;
-                for (int e = threadIdx.x; e < 32 * kRecStride / 2; e += 256)
-                    if (r0 * (kRecStride / 2) + e >= 0) dst[e] = src[(int64_t)r0 * (kRecStride / 2) + e];
-                __syncthreads();
-                skip = qtry && __builtin_amdgcn_readfirstlane(qskip_blk[pk & 1]) != 0;
-            }
-#else
             // (round 6) each wave votes before the barrier that ends the previous panel; a
             // panel the block skips stages no records (the weight terms are read from the
             // record array in memory) and needs no second barrier
@@ -1536,7 +1142,6 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? LGS_OZ_LB : LGS_MFMA_LB32) : 
                     if (r0 * (kRecStride / 2) + e >= 0) dst[e] = src[(int64_t)r0 * (kRecStride / 2) + e];
                 __syncthreads();
             }
-#endif
             if (!active) continue;
             if (skip) {
                 if (lane == 0) atomicAdd(a.flags + kFlagWordQSkip, 1u);
@@ -1570,19 +1175,13 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? LGS_OZ_LB : LGS_MFMA_LB32) : 
         // of ref_weight cancel to rounding), and the one-dominant-point margin of these
         // sigma_i ~ 1e-2 coordinates dwarfs the larger bound.
         bool coarse = false;
-#ifndef LGS_NO_COARSE
         if constexpr (OZ && PB == 32 && !WL)
             coarse = p_hi >= 32 &&
                      __builtin_amdgcn_readfirstlane((int)((lds_cdptr)rec_lds)[31 * kRecStride + kRecSpec]) == 1 &&
                      __builtin_amdgcn_readfirstlane((int)((lds_cdptr)rec_lds)[15 * kRecStride + kRecSpec]) == 1;
-#endif
         LGS_DC_T(t_far0);
         LGS_DC_ADD(0, t_far0 - t_panel0);
-#ifdef LGS_DIAG_NO_FAR
-        if (false) {
-#else
         if (pk > 0) {
-#endif
             // far field on the matrix cores; coefficients of rows >= p_hi were
             // stored by this wave's lanes in earlier panels
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1693,122 +1292,7 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? LGS_OZ_LB : LGS_MFMA_LB32) : 
             // still in flight at a SampleZ call would be waited for at the callee's
             // entry (the calling convention starts with s_waitcnt 0).
             bool pnz = false;  // (OZ) a nonzero coefficient in this panel, this lane
-#ifdef LGS_NEAR_UNROLLED  // the round-2 near field: 16 steps unrolled, SampleZ as leaf calls
-            auto near16 = [&](int rows16, int top) __attribute__((always_inline)) {
-                using ZH = std::conditional_t<sizeof(ZT) == 8, double, int>;
-                ZH zh[16];
-                cert_lds[1][threadIdx.x] = cert_lds[0][threadIdx.x];  // sum |z_j| before the sub-panel
-                cert_lds[2][threadIdx.x] = lw;
-#pragma unroll
-                for (int s = 0; s < 16; ++s) {
-                    if (s < rows16) {
-                        const int i = __builtin_amdgcn_readfirstlane(top - 1 - s);
-                        const lds_cdptr rec = (lds_cdptr)rec_lds + (i - (p_hi - 32)) * kRecStride;
-                        // running sums rotate instead of shifting: logical acc[k] of step s
-                        // lives in acc[(k - s) & 15] (s is a compile-time constant here), so
-                        // no register moves per coordinate; 16 steps bring the map back
-                        // Ca, Cb, c', 1/R_ii (record slots 21..24) in two 16-byte LDS reads
-                        static_assert(kSzCa == 21 && kSzCb == 22 && kRecCp == 23 && kRecIrii == 24, "record layout");
-                        typedef double d2v __attribute__((ext_vector_type(2)));
-                        const RecRegs rr = load_rec(rec);
-                        const double mu = (rr[kRecCp] - acc[(15 - s) & 15]) * rr[kRecIrii];
-                        LGS_DC_T(t_sz0);
-                        // certified decision at the blocked-order mean (the |z| sum
-                        // bounded by the cap a.z1cap, checked after the sub-panel); a
-                        // decision not covered is a guess, verified after the sub-panel
-                        bool un;
-                        const double zi = decide_coord_rec<WL, true, LIBM>(a, i, mu, rec, rr, rs, lw, flags, etab_s,
-                                                                     cert_dmu(rr[kSzCa], rr[kSzCb], a.z1cap, mu),
-                                                                     un, eb, tb);
-                        if (un) cert_fl[threadIdx.x] |= 1 << s;
-#ifdef LGS_DIAG_CYCLES
-                        {
-                            LGS_DC_T(t_sz1);
-                            const int kind = (int)rec[2] & 7;
-                            LGS_DC_ADD(3 + kind, t_sz1 - t_sz0);
-                            LGS_DC_ADD(8 + kind, 1);
-                        }
-#endif
-                        if constexpr (sizeof(ZT) == 8) {
-                            zh[s] = zi;
-                        } else {
-                            if (sizeof(ZT) == 4 && !(zi <= 2147483647.0 && zi >= -2147483648.0))
-                                flags |= kFlagOverflow;
-                            if (sizeof(ZT) == 2 && !(zi <= 32767.0 && zi >= -32768.0)) flags |= kFlagOverflow16;
-                            zh[s] = (int)fmin(fmax(zi, -2147483648.0), 2147483647.0);
-                        }
-                        if constexpr (OZ)
-                            if (!(zi <= 32639.0 && zi >= -32767.0)) flags |= kFlagOverflow16;
-#pragma unroll
-                        for (int k = 0; k < 15; ++k) acc[(k - s) & 15] = fma(rr[kRecRs + 14 - k], zi, acc[(k - s) & 15]);
-                        acc[(15 - s) & 15] = 0.0;  // the next step's logical acc[0]
-                    }
-                }
-                // int16 history value (z + 128, clamped to the far field's digit range)
-                auto hist_val = [&](int s) -> int {
-                    if constexpr (sizeof(ZT) == 8)
-                        return (int)(fmin(fmax(zh[s], -32767.0), 32639.0) + 128.0);
-                    else
-                        return min(max(zh[s], -32767), 32639) + 128;
-                };
-                // a whole sub-panel is one 16-coordinate history block ((top + shift) % 16
-                // == 0; position 15 - s holds row top - 1 - s): two 16-byte stores
-                const bool hblock = OZ && rows16 == 16;
-#pragma unroll
-                for (int s = 0; s < 16; ++s) {
-                    if (s < rows16) {
-                        const int i = top - 1 - s;
-                        if constexpr (sizeof(ZT) == 8)
-                            Z[(size_t)i * ldz + p] = (ZT)(int64_t)zh[s];
-                        else
-                            Z[(size_t)i * ldz + p] = (ZT)zh[s];
-                        if constexpr (OZ) {  // int16 history (z + 128) for the int8-digit far field
-                            if (!hblock) {
-                                const int ih = i + a.h16_shift;
-                                a.h16[((size_t)(ih >> 4) * a.h16_lanes + p) * 16 + (ih & 15)] = (int16_t)hist_val(s);
-                            }
-                            pnz |= zh[s] != 0;
-                        }
-                    }
-                }
-                if constexpr (OZ) {
-                    if (hblock) {
-                        v4u_t h[2];
-#pragma unroll
-                        for (int j = 0; j < 8; ++j)
-                            h[j >> 2][j & 3] = ((unsigned int)hist_val(15 - 2 * j) & 0xffffu) |
-                                               ((unsigned int)hist_val(14 - 2 * j) << 16);
-                        v4u_t* hp = (v4u_t*)(a.h16 + ((size_t)((top - 16 + a.h16_shift) >> 4) * a.h16_lanes + p) * 16);
-                        hp[0] = h[0];
-                        hp[1] = h[1];
-                    }
-                }
-                {
-                    // the certificate used sum_{j>i} |z_j| <= z1cap: verify it (the sum at
-                    // the sub-panel's end bounds every coordinate's) -- else replay
-                    double z1e = cert_lds[1][threadIdx.x];  // (re-read: not live across the sub-panel)
-#pragma unroll
-                    for (int s = 0; s < 16; ++s)
-                        if (s < rows16) z1e += fabs((double)zh[s]);
-                    cert_lds[0][threadIdx.x] = z1e;
-                }
-                const int fl = cert_fl[threadIdx.x] | (cert_lds[0][threadIdx.x] > a.z1cap ? (1 << 16) : 0);
-                if (__builtin_amdgcn_ballot_w64(fl != 0) != 0) {  // rare: verify / replay (whole wave)
-                    cert_fl[threadIdx.x] = 0;
-                    const int w64 = threadIdx.x & ~63;
-                    const VerifyOut vo = verify_subpanel<WL, OZ>(kernel_args(), Z, ldz, p0, top, rows16, fl, lw,
-                                                                 rs.step, rs.chain, &cert_lds[0][w64],
-                                                                 &cert_lds[1][w64], &cert_lds[2][w64], flags);
-                    lw = vo.lw;
-                    flags = vo.flags;
-                    if (WL) tb += vo.tabs;
-                    if constexpr (OZ) pnz |= vo.nz != 0;
-                }
-                if constexpr (OZ)  // (this variant keeps no per-sub-panel flag: the block counts as nonzero)
-                    if (a.znz) a.znz[(size_t)((top - 1 + a.h16_shift) >> 4) * a.h16_lanes + p] = 1;
-            };
-#endif
-            // Rolled near field (default): one loop iteration per coordinate with the
+            // Rolled near field: one loop iteration per coordinate with the
             // decision inline -- no call in the hot path, so no SGPR spill / restore
             // around it, no wait-for-everything at a callee's entry, and the record
             // loads of the next steps can be scheduled under the current decision.
@@ -1821,19 +1305,14 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? LGS_OZ_LB : LGS_MFMA_LB32) : 
                 cert_lds[1][threadIdx.x] = cert_lds[0][threadIdx.x];  // sum |z_j| before the sub-panel
                 cert_lds[2][threadIdx.x] = lw;
                 double z1e = cert_lds[0][threadIdx.x];
-#ifdef LGS_HIST_STORE16
-                // (default) every coordinate's history value stored at once: the packing of a
+                // every coordinate's history value stored at once: the packing of a
                 // whole sub-panel through 8 registers (8 VALU per coordinate) cost more than
                 // the 16-bit store it saves (profiles/r05f_kb_trims.log)
                 const bool hblock = false;
-#else
-                const bool hblock = OZ && rows16 == 16;
-#endif
                 unsigned int hp[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) hp[j] = 0u;
                 int flm = 0;
-#ifndef LGS_NO_CAP_SP
                 // the whole sub-panel is capped with sigma >= 360 (host flag kRecSpec == 2):
                 // its steps take the capped decision without the per-coordinate kind
                 // dispatch (round 6, with the scheduler flags: C3 / C4 / C5 Klein -2.9 / -1.2
@@ -1843,65 +1322,33 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? LGS_OZ_LB : LGS_MFMA_LB32) : 
                 // its certificate uses the sub-panel's own Cb.
                 const int capsp = !LIBM && rows16 == 16 &&
                                   __builtin_amdgcn_readfirstlane((int)((lds_cdptr)rec_lds)[(top - 1 - (p_hi - 32)) * kRecStride + kRecSpec]) == 2;
-#endif
                 bool snz = false;  // (OZ) a nonzero z in this sub-panel, this lane
-#ifdef LGS_TAIL3
                 int izmx = 0, izmn = 0;  // (16-bit stores) the same extremes of the saturated int32 values
                 int16_t* hptr = a.h16 + ((size_t)((top - 1 + a.h16_shift) >> 4) * a.h16_lanes + p) * 16 +
                                 ((top - 1 + a.h16_shift) & 15);
-#endif
-#ifdef LGS_TAIL2
                 double zmx = 0.0, zmn = 0.0;  // the sub-panel's largest / smallest z (range checks, snz)
                 ZT* zrow = Z + (size_t)(top - 1) * ldz;  // row of the step's coordinate (uniform)
                 const uint32_t zoff = (uint32_t)p * (uint32_t)sizeof(ZT);  // this lane's byte offset in a row
-#endif
                 double zsq = 0.0;  // (q-panel skip) sum z^2 of this sub-panel, this lane
-#ifndef LGS_NEAR_UNROLL  // coordinates per loop iteration (the running sums shift by one per step)
-#define LGS_NEAR_UNROLL 1
-#endif
-#pragma unroll LGS_NEAR_UNROLL
+#pragma unroll 1
                 for (int s = 0; s < rows16; ++s) {
-#ifdef LGS_DIAG_STEP  // diagnostic builds only: phases of a near-field step (lgs_diag_cycles [3] [4] [5])
-                    LGS_DC_T(t_stepA);
-#endif
                     const int i = __builtin_amdgcn_readfirstlane(top - 1 - s);
                     const lds_cdptr rec = (lds_cdptr)rec_lds + (i - (p_hi - 32)) * kRecStride;
                     static_assert(kSzCa == 21 && kSzCb == 22 && kRecCp == 23 && kRecIrii == 24, "record layout");
-#if defined(LGS_DBG1) || defined(LGS_PHILOX_TOP)
-                    // (LGS_DBG1: the round-4 hazard reconstruction; LGS_PHILOX_TOP:
-                    // the same placement as an optimisation) the coordinate's Philox block drawn
-                    // under the record's LDS reads, off the decision's dependency chain
-                    const RecRegs rr = load_rec(rec, [&]() { (void)rs.u((uint32_t)(d - 1 - i)); });
-#elif defined(LGS_REC_SMEM)
-                    const RecRegs rr = load_rec_g(cst(a.crec) + (size_t)i * kRecStride);
-#elif defined(LGS_REC_RS_SMEM)
-                    const RecRegs rr = load_rec(rec, cst(a.crec) + (size_t)i * kRecStride);
-#else
                     const RecRegs rr = load_rec(rec);
-#endif
                     const double mu = (rr[kRecCp] - acc[15]) * rr[kRecIrii];
                     LGS_DC_T(t_sz0);
                     bool un;
-#ifndef LGS_NO_CAP_SP
                     int cf = __builtin_amdgcn_readfirstlane(capsp);
                     asm volatile("" : "+s"(cf));  // a scalar test per step (no loop unswitching: one copy of the loop)
                     const double zi = cf ? decide_capped_rec<WL>(a, i, mu, rec, rr, rs, lw, flags, etab_s,
                                                                  cert_dmu(rr[kSzCa], rr[kSzCb], a.z1cap, mu), un, eb, tb)
                                          : decide_coord_rec<WL, true, LIBM>(
                                                a, i, mu, rec, rr, rs, lw, flags, etab_s,
-                                               cert_dmu(rr[kSzCa], coarse ? REC_CBC : rr[kSzCb], a.z1cap, mu), un,
+                                               cert_dmu(rr[kSzCa], coarse ? rr[kRecCbC] : rr[kSzCb], a.z1cap, mu), un,
                                                eb, tb);
-#else
-                    const double zi = decide_coord_rec<WL, true, LIBM>(
-                        a, i, mu, rec, rr, rs, lw, flags, etab_s,
-                        cert_dmu(rr[kSzCa], coarse ? REC_CBC : rr[kSzCb], a.z1cap, mu), un, eb, tb);
-#endif
-#ifdef LGS_TAIL3
                     if (__builtin_amdgcn_ballot_w64(un) != 0) flm |= un ? (1 << s) : 0;  // (rare)
-#else
-                    flm |= un ? (1 << s) : 0;
-#endif
-#if defined(LGS_DIAG_CYCLES) && !defined(LGS_DIAG_STEP)
+#ifdef LGS_DIAG_CYCLES
                     {
                         LGS_DC_T(t_sz1);
                         const int kind = (int)rec[2] & 7;
@@ -1909,16 +1356,11 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? LGS_OZ_LB : LGS_MFMA_LB32) : 
                         LGS_DC_ADD(8 + kind, 1);
                     }
 #endif
-#ifdef LGS_DIAG_STEP
-                    LGS_DC_T(t_stepC);
-#endif
                     // stores: v_cvt_i32_f64 saturates, so no clamps -- a value beyond the
                     // int16 history's range (or a 16-bit store's) flags kFlagOverflow16 and
                     // the launch is redone wider; beyond int32 is an error (kFlagOverflow)
-#ifdef LGS_TAIL2
                     // (the range checks from the sub-panel's extremes after the loop; the store
                     // through the row's uniform base and a 32-bit lane offset)
-#ifdef LGS_TAIL3
                     // 16-bit stores: the extremes of the saturated int32 conversion (one
                     // v_max_i32 / v_min_i32; fmax would canonicalise both operands first)
                     // detect every value outside the int16 / history range as well
@@ -1930,29 +1372,12 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? LGS_OZ_LB : LGS_MFMA_LB32) : 
                         zmx = fmax(zmx, zi);
                         zmn = fmin(zmn, zi);
                     }
-#else
-                    const int zint = (int)zi;
-                    zmx = fmax(zmx, zi);
-                    zmn = fmin(zmn, zi);
-#endif
                     if constexpr (sizeof(ZT) == 8)
                         *(ZT*)((char*)zrow + zoff) = (ZT)(int64_t)zi;
                     else
                         *(ZT*)((char*)zrow + zoff) = (ZT)zint;
                     zrow -= ldz;
-#else
-                    if constexpr (sizeof(ZT) == 8) {
-                        Z[(size_t)i * ldz + p] = (ZT)(int64_t)zi;
-                    } else {
-                        if (sizeof(ZT) == 4 && !(zi <= 2147483647.0 && zi >= -2147483648.0)) flags |= kFlagOverflow;
-                        if (!OZ && sizeof(ZT) == 2 && !(zi <= 32767.0 && zi >= -32768.0)) flags |= kFlagOverflow16;
-                        Z[(size_t)i * ldz + p] = (ZT)(int)zi;
-                    }
-#endif
                     if constexpr (OZ) {
-#ifndef LGS_TAIL2
-                        if (!(zi <= 32639.0 && zi >= -32767.0)) flags |= kFlagOverflow16;
-#endif
                         // int16 history value z + 128 (exact whenever the range check passed)
                         const unsigned int hv = (unsigned int)((int)zi + 128) & 0xffffu;
                         if (hblock) {
@@ -1960,20 +1385,12 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? LGS_OZ_LB : LGS_MFMA_LB32) : 
                             for (int j = 7; j >= 1; --j) hp[j] = __builtin_amdgcn_alignbit(hp[j], hp[j - 1], 16);
                             hp[0] = (hp[0] << 16) | hv;
                         } else {
-#ifdef LGS_TAIL3
                             // a sub-panel lies in one 16-coordinate history block ((top + shift)
                             // % 16 == 0): step s writes position 15 - s of this lane's block
                             *hptr = (int16_t)hv;
                             --hptr;
-#else
-                            const int ih = i + a.h16_shift;
-                            a.h16[((size_t)(ih >> 4) * a.h16_lanes + p) * 16 + (ih & 15)] = (int16_t)hv;
-#endif
                             if constexpr (!WL) zsq = fma(zi, zi, zsq);  // (whole sub-panels: from hp below)
                         }
-#ifndef LGS_TAIL2
-                        snz |= zi != 0.0;
-#endif
                     }
                     // sum |z|: only the sub-panel's end reads it (the certificate's per-coordinate
                     // bound uses the cap), so a whole 16-row sub-panel takes it from the packed
@@ -1983,30 +1400,15 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? LGS_OZ_LB : LGS_MFMA_LB32) : 
 #pragma unroll
                     for (int k = 14; k >= 0; --k) acc[k + 1] = fma_shift(rr[kRecRs + 14 - k], zi, acc[k]);
                     acc[0] = 0.0;
-#ifdef LGS_DIAG_STEP
-                    {
-                        LGS_DC_T(t_stepD);
-                        LGS_DC_ADD(3, t_sz0 - t_stepA);  // record batch + mean
-                        LGS_DC_ADD(4, t_stepC - t_sz0);  // decision (kind dispatch, Philox, SampleZ, weight)
-                        LGS_DC_ADD(5, t_stepD - t_stepC);  // stores, history packing, bookkeeping, 15 FMAs
-                        LGS_DC_ADD(8, 1);
-                        LGS_DC_ADD(9, 1);
-                        LGS_DC_ADD(10, 1);
-                    }
-#endif
                 }
-#ifdef LGS_TAIL3
                 if constexpr (sizeof(ZT) <= 2) {
                     zmx = (double)izmx;
                     zmn = (double)izmn;
                 }
-#endif
-#ifdef LGS_TAIL2
                 if (sizeof(ZT) == 4 && !(zmx <= 2147483647.0 && zmn >= -2147483648.0)) flags |= kFlagOverflow;
                 if (!OZ && sizeof(ZT) == 2 && !(zmx <= 32767.0 && zmn >= -32768.0)) flags |= kFlagOverflow16;
                 if (OZ && !(zmx <= 32639.0 && zmn >= -32767.0)) flags |= kFlagOverflow16;
                 if constexpr (OZ) snz = zmx != 0.0 || zmn != 0.0;
-#endif
                 if constexpr (OZ) {
                     if (hblock) {
                         v4u_t* hp4 = (v4u_t*)(a.h16 + ((size_t)((top - 16 + a.h16_shift) >> 4) * a.h16_lanes + p) * 16);
@@ -2041,23 +1443,19 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? LGS_OZ_LB : LGS_MFMA_LB32) : 
                     if constexpr (OZ) snz |= vo.nz != 0;
                     if (vo.z2 >= 0.0) zsq = vo.z2;
                 }
-#ifndef LGS_NO_QSKIP_CODE
                 if constexpr (OZ && !WL) {  // the q-panel skip's ||z_W||^2 (+inf: a speculative z != 0)
                     const bool spec_sp = rows16 == 16 &&
                                          __builtin_amdgcn_readfirstlane((int)((lds_cdptr)rec_lds)[(top - 1 - (p_hi - 32)) * kRecStride + kRecSpec]) == 1;
                     qzs[threadIdx.x] = spec_sp ? (zsq != 0.0 ? __builtin_inf() : qzs[threadIdx.x]) : qzs[threadIdx.x] + zsq;
                 }
-#endif
                 if constexpr (OZ) {
                     pnz |= snz;
                     if (a.znz) a.znz[(size_t)((top - 1 + a.h16_shift) >> 4) * a.h16_lanes + p] = snz ? 1 : 0;
                     // the wave's 64-coordinate chunk of these rows holds a nonzero (B z skips
                     // the others with one word per 32 chunks, not one flag load per chunk)
-#ifndef LGS_NO_CLIVE_K
                     if (a.clive && top >= 16 && __builtin_amdgcn_ballot_w64(snz) != 0 && lane == 0)
                         atomicOr(a.clive + (size_t)((top - 16) >> 11) * a.clive_ld + (p0 >> 6),
                                  1u << (((top - 16) >> 6) & 31));
-#endif
                 }
             };
             // one copy of the 16-step near field for both sub-panels (a second inlined
@@ -2089,11 +1487,7 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? LGS_OZ_LB : LGS_MFMA_LB32) : 
                     for (int kk = 0; kk < 4; ++kk) {
                         const double av = rx[64 * kk];
                         ZQuad<ZT> q;
-#ifdef LGS_DIAG_COUPLE_NOLOAD  // diagnostic builds only (NOT bit-exact): the coupling without its Z reload
-                        q.load(Z + p0 + 4 * nq);
-#else
                         q.load(zu + (size_t)(4 * kk) * ldz);
-#endif
 #pragma unroll
                         for (int g = 0; g < 4; ++g)
                             c[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, q.get(g), c[g], 0, 0, 0);
@@ -2165,11 +1559,7 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? LGS_OZ_LB : LGS_MFMA_LB32) : 
                     }
                 }
 #endif
-#ifdef LGS_NEAR_UNROLLED
-                near16(rows16, top);
-#else
                 near16r(rows16, top);
-#endif
             }
             if constexpr (OZ) {  // visible to the block at the next panel's staging barrier
                 if (__builtin_amdgcn_ballot_w64(pnz) != 0 && lane == 0) atomicOr(&nzm[pk >> 5], 1u << (pk & 31));
@@ -3411,17 +2801,12 @@ __device__ __forceinline__ unsigned long long dpp_row_ror_u64(unsigned long long
     return ((unsigned long long)hi << 32) | lo;
 }
 
-#ifndef LGS_BZ_OCC
-#define LGS_BZ_OCC 3  // (round 5: pinned to three workgroups per CU; unpinned the int32 store instantiation drifted to 174 VGPRs)
-#endif
-#ifndef LGS_BZ_TXPER
-#define LGS_BZ_TXPER 1
-#endif
-#ifndef LGS_BZ_TA
-#define LGS_BZ_TA 1
-#endif
+// (round 5: pinned to three workgroups per CU; unpinned the int32 store instantiation drifted to 174 VGPRs)
+constexpr int kBzOcc = 3;
+constexpr int kBzTxPer = 1;  // consecutive coordinate tiles per workgroup
+constexpr int kBzTA = 1;     // 32-sample MFMA tiles per wave: 64 kBzTA samples per workgroup (the history path needs 1)
 template <typename ZT>
-__global__ __launch_bounds__(256, LGS_BZ_OCC) void bz_i8_kernel(const ZT* __restrict__ Z, int64_t ldz,
+__global__ __launch_bounds__(256, kBzOcc) void bz_i8_kernel(const ZT* __restrict__ Z, int64_t ldz,
                                                     const int64_t* __restrict__ sel,
                                                     const int* __restrict__ kchunk,
                                                     const int* __restrict__ koff,
@@ -3438,7 +2823,7 @@ __global__ __launch_bounds__(256, LGS_BZ_OCC) void bz_i8_kernel(const ZT* __rest
                                                     unsigned long long* __restrict__ MP, int64_t mp_ld,
                                                     unsigned int* __restrict__ MPL) {
     if (aborted(abort)) return;  // (whole grid) the selections were not written
-    constexpr int TA = LGS_BZ_TA;  // 32-sample MFMA tiles per wave
+    constexpr int TA = kBzTA;  // 32-sample MFMA tiles per wave
     constexpr int BM = 64 * TA, BN = kBzBN, KC = 64, P = 80;  // P: LDS row pitch (bytes), conflict-free
     constexpr int TN = BN / 64;  // 32-coordinate MFMA tiles per wave (waves 2 x 2)
     constexpr int KPT = KC * BM / 256;  // coefficients per thread per chunk
@@ -3449,7 +2834,7 @@ __global__ __launch_bounds__(256, LGS_BZ_OCC) void bz_i8_kernel(const ZT* __rest
     // workgroup b runs on XCD b % 8; the tx_count coordinate tiles of one sample
     // tile are given to consecutive workgroups of the same XCD, which then reads
     // that sample tile's coefficients from HBM once and from its own L2 after.
-    // Each workgroup computes LGS_BZ_TXPER consecutive coordinate tiles of its
+    // Each workgroup computes kBzTxPer consecutive coordinate tiles of its
     // sample tile, so the output stores of one tile drain while the MFMAs of the
     // next one run.
     const int64_t b = blockIdx.x, w = b >> 3;
@@ -3459,7 +2844,7 @@ __global__ __launch_bounds__(256, LGS_BZ_OCC) void bz_i8_kernel(const ZT* __rest
     const int64_t s0 = ty * BM;
     const int ntx = (d + BN - 1) / BN;
     ZT zmax = 0, zmin = 0;  // range of the coefficients read (exactness check)
-    for (int tx = txg * LGS_BZ_TXPER; tx < ntx && tx < (txg + 1) * LGS_BZ_TXPER; ++tx) {
+    for (int tx = txg * kBzTxPer; tx < ntx && tx < (txg + 1) * kBzTxPer; ++tx) {
     const int r0 = tx * BN;
     v16i_t p1[TA][TN], p2[TA][TN], p3[TA][TN];
 #pragma unroll
@@ -3476,11 +2861,7 @@ __global__ __launch_bounds__(256, LGS_BZ_OCC) void bz_i8_kernel(const ZT* __rest
     // only the K chunks where this row tile of B has a non-zero digit (exact skip)
     // (the block-sparsity lists are per 128-row tile of B)
     const int ci0 = koff[tx * BN / 128];
-#ifdef LGS_DIAG_BZ_NOMFMA  // diagnostic builds only: epilogue cost probe
-    const int ci1 = ci0;
-#else
     const int ci1 = koff[tx * BN / 128 + 1];
-#endif
     // Chunks where every sample of the tile has z = 0 on all 64 coordinates contribute
     // exactly nothing: skipped.  The Klein launch that wrote the history flags each
     // (16-coordinate block, sample) holding a nonzero (znz); thread (zm, zq) checks
@@ -3502,24 +2883,18 @@ __global__ __launch_bounds__(256, LGS_BZ_OCC) void bz_i8_kernel(const ZT* __rest
     if (use_clive) {
         {
             const int ng = ngw;
-#ifndef LGS_BZ_NO_GUESS
             // the word of the identity selection (row q = proposal q: every kept state a
             // fresh proposal, e.g. acceptance 1) is loaded beside the selection itself
             // instead of after it; a lane whose selection differs reloads
             const int64_t zg = zs_ < n ? zs_ : 0;
             const unsigned int wg0 = zg < hcols ? clive[zg >> 6] : 0xffffffffu;
             const bool same = (zcol >> 6) == (zg >> 6) && (zcol < hcols) == (zg < hcols);
-#endif
             for (int g = 0; g < ng; ++g) {
                 unsigned int w = 0u;
-#ifndef LGS_BZ_NO_GUESS
                 const unsigned int wg =
                     g == 0 ? wg0 : (zg < hcols ? clive[(size_t)g * clive_ld + (zg >> 6)] : 0xffffffffu);
                 if (zs_ < n)
                     w = same ? wg : (zcol < hcols ? clive[(size_t)g * clive_ld + (zcol >> 6)] : 0xffffffffu);
-#else
-                if (zs_ < n) w = zcol < hcols ? clive[(size_t)g * clive_ld + (zcol >> 6)] : 0xffffffffu;
-#endif
                 // OR over the wave's lanes; all equal (the tile's samples from one Klein
                 // wave) needs no shuffles
                 const unsigned int w0 = __builtin_amdgcn_readfirstlane(w);
@@ -3626,8 +3001,8 @@ __global__ __launch_bounds__(256, LGS_BZ_OCC) void bz_i8_kernel(const ZT* __rest
             // (round 5) the kept states' moments ride on this tile's digit planes while the
             // MFMAs run (round 6: called after the chunk's MFMAs are issued, so the VALU work
             // runs under the matrix pipe -- with the 16-byte stores below, B z 7.19 -> 6.98 ms
-            // per 2^22 lattice points, profiles/r06q_bz_ab.log; LGS_BZ_MOM_EARLY: ahead of
-            // them): wave w sums coordinates 16w..16w+15 of the chunk over the tile's 64
+            // per 2^22 lattice points, profiles/r06q_bz_ab.log):
+            // wave w sums coordinates 16w..16w+15 of the chunk over the tile's 64
             // rows, lane (4 coordinates: lane >> 4) x (4 rows: lane & 15), packed per row as
             // z^2 * 2^24 + (z + 32768) (64 rows: the low field < 2^22, the total < 2^63;
             // rows past n hold z = 0 and add the bias only), then over the 16 lanes of a
@@ -3658,9 +3033,6 @@ __global__ __launch_bounds__(256, LGS_BZ_OCC) void bz_i8_kernel(const ZT* __rest
                 for (int j = 0; j < 4; ++j) mp[j] = ps[j];
             }
         };
-#ifdef LGS_BZ_MOM_EARLY
-        if (mown) moment_partials();
-#endif
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const int kb = ks * 32 + 16 * (lane >> 5);
@@ -3685,9 +3057,7 @@ __global__ __launch_bounds__(256, LGS_BZ_OCC) void bz_i8_kernel(const ZT* __rest
                 }
             }
         }
-#ifndef LGS_BZ_MOM_EARLY
         if (mown) moment_partials();
-#endif
         __syncthreads();
     }
     // output rows: sample q -> (q / rb) * rstride + roff + q % rb.  The wave's 32
@@ -3742,7 +3112,6 @@ __global__ __launch_bounds__(256, LGS_BZ_OCC) void bz_i8_kernel(const ZT* __rest
     const int64_t cb = qb / rb;
     const int64_t kb0 = qb - cb * rb;
     const int nrow = (int)min<int64_t>(n - qb, 32);  // valid rows of this tile
-#ifndef LGS_BZ_NARROW
     // (round 6, with the moments after the MFMAs: B z 7.19 -> 6.98 ms per 2^22 lattice
     // points, profiles/r06q_bz_ab.log) 16-byte stores: lanes 2c and 2c + 1 swap one value per pair of rows
     // (DPP quad_perm [1, 0, 3, 2]), so the even lane holds row r, columns 2c and 2c + 1
@@ -3777,7 +3146,6 @@ __global__ __launch_bounds__(256, LGS_BZ_OCC) void bz_i8_kernel(const ZT* __rest
             }
         }
     } else
-#endif
     if (rb >= 32) {
         const int wrap_row = (int)min<int64_t>(rb - kb0, 32);  // first row past the boundary
         double* const vbase = V + (size_t)(cb * rstride + roff + kb0) * ldv + r0 + wn * (BN / 2) + (lane & 31);
@@ -3792,9 +3160,6 @@ __global__ __launch_bounds__(256, LGS_BZ_OCC) void bz_i8_kernel(const ZT* __rest
                 if (r0 + wn * (BN / 2) + tn * 32 + (lane & 31) < d) {
                     const double v = fma((double)p1[ta][tn][reg], 65536.0, (double)p2[ta][tn][reg] * 256.0) +
                                      (double)p3[ta][tn][reg];
-#ifdef LGS_DIAG_BZ_NOSTORE  // diagnostic builds only: store cost probe
-                    if (v == 0.5)
-#endif
                     __builtin_nontemporal_store(v, vrow + tn * 32);  // streamed out, not re-read
                 }
             }
@@ -4101,14 +3466,8 @@ hipError_t moments_final(const void* Z, int zb, int64_t ldz, const int32_t* cnt,
                          const uint8_t* znz, int64_t zlanes, int zshift, const unsigned int* need) {
     if (n <= 0) return hipSuccess;
     if (zb != 2 || zlanes % 8 != 0) znz = nullptr;  // (8 proposals per flag load, 16-bit store only)
-#ifdef LGS_MOM_NO_ZNZ
-    znz = nullptr;
-#endif
     const int64_t chunk = 16384;  // multiple of 4
-#ifndef LGS_MOM_RY
-#define LGS_MOM_RY 4
-#endif
-    constexpr int RY = LGS_MOM_RY;  // rows per workgroup, vector path
+    constexpr int RY = 4;  // rows per workgroup, vector path
     dim3 grid((unsigned)((n + chunk - 1) / chunk), (unsigned)d);
     dim3 gridv((unsigned)((n + chunk - 1) / chunk), (unsigned)((d + RY - 1) / RY));
     if (need) {  // gated fallback: a small grid that returns at once unless needed
@@ -4382,26 +3741,14 @@ hipError_t bz_i8(const void* Z, int zb, int64_t ldz, const int64_t* sel, const i
                  unsigned int* MPL) {
     if (n <= 0) return hipSuccess;
     if (vn_n <= 0) VNP = nullptr;
-    if (d % 16 != 0 || LGS_BZ_TA != 1 || d > kOzMaxD) h16 = nullptr;  // history blocks must align with the chunks
-#ifdef LGS_BZ_NO_ZNZ
-    znz = nullptr;
-#endif
+    if (d % 16 != 0 || kBzTA != 1 || d > kOzMaxD) h16 = nullptr;  // history blocks must align with the chunks
     if (h16 == nullptr) znz = nullptr;
     if (h16 == nullptr) clive = nullptr;
-#ifdef LGS_BZ_NO_CLIVE
-    clive = nullptr;
-#endif
     // the moment partials (MP / MPL) are written on the clive path only: never hand
     // bz_moments_reduce partials this launch will not write
-    if (MP != nullptr && (clive == nullptr || !bz_moments_supported())) return hipErrorInvalidValue;
-#ifdef LGS_DIAG_BZ_NO_VNP  // diagnostic builds only: epilogue cost of the ||v||^2 partial sums
-    VNP = nullptr;
-#endif
-#ifdef LGS_DIAG_BZ_NO_SEL  // diagnostic builds only (identity selections, e.g. acceptance 1): gather cost
-    sel = nullptr;
-#endif
-    const int tx = ((d + kBzBN - 1) / kBzBN + LGS_BZ_TXPER - 1) / LGS_BZ_TXPER;  // coordinate-tile groups
-    const int64_t ty = (n + 64 * LGS_BZ_TA - 1) / (64 * LGS_BZ_TA);
+    if (MP != nullptr && clive == nullptr) return hipErrorInvalidValue;
+    const int tx = ((d + kBzBN - 1) / kBzBN + kBzTxPer - 1) / kBzTxPer;  // coordinate-tile groups
+    const int64_t ty = (n + 64 * kBzTA - 1) / (64 * kBzTA);
     const dim3 grid((unsigned)(tx * ((ty + 7) / 8) * 8));  // whole rounds of 8 XCDs (extra tiles exit)
     LGS_ZT(zb, ZT, hipLaunchKernelGGL(bz_i8_kernel<ZT>, grid, dim3(256), 0, st, (const ZT*)Z, ldz, sel, kchunk, koff, Bd1, Bd0, dc, d, n, V, ldv, rb, rstride, roff, flags, tx, ty, h16, h16_lanes, hcols, abort, znz, clive, clive_ld, VNP, vn_n, MP, mp_ld, MPL));
     return hipGetLastError();

@@ -195,3 +195,27 @@ def test_imhk_outputs_struct_matches_header():
     names = re.findall(r"\*?(\w+);", body)
     assert names == [f[0] for f in _capi.ImhkOutputs._fields_]
     assert ctypes.sizeof(_capi.ImhkOutputs) == 8 * len(names)
+
+
+def test_compile_time_switches_are_the_listed_ones():
+    """Every LGS_* name a preprocessor conditional of csrc/ tests is a switch in the list
+    at the top of lgs_kernels.h or a macro csrc/ itself #defines, and every listed switch
+    is still tested somewhere: an experiment switch cannot come back unlisted."""
+    import glob
+    csrc = os.path.join(REPO, "lattice-gaussian-mcmc_amd", "csrc")
+    head = open(os.path.join(csrc, "lgs_kernels.h")).read()
+    block = re.search(r"^// Compile-time switches.*?\n((?://.*\n)+)", head, re.M).group(1)
+    listed = set(re.findall(r"^//   (LGS_[A-Z0-9_]+)\s", block, re.M))
+    assert listed, "the switch list at the top of lgs_kernels.h was not found"
+    tested, defined = {}, set()
+    for path in sorted(glob.glob(os.path.join(csrc, "*"))):
+        for no, line in enumerate(open(path), 1):
+            if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                for name in re.findall(r"LGS_[A-Z0-9_]+", line.split("//")[0]):
+                    tested.setdefault(name, f"{os.path.basename(path)}:{no}")
+            m = re.match(r"\s*#\s*define\s+(LGS_[A-Z0-9_]+)", line)
+            if m:
+                defined.add(m.group(1))
+    unlisted = {n: w for n, w in tested.items() if n not in listed and n not in defined}
+    assert not unlisted, f"conditionals on switches missing from the list in lgs_kernels.h: {unlisted}"
+    assert listed <= set(tested), f"listed but tested nowhere: {sorted(listed - set(tested))}"
