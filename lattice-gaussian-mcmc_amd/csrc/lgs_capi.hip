@@ -145,6 +145,7 @@ struct lgs_ctx {
     uint64_t n_qskip = 0;  // (wave, panel) pairs decided by the q-panel skip
     uint64_t n_decode_resolved = 0;  // lgs_klein_decode: targets whose winner the bounds did not decide
     uint64_t n_fallback = 0;      // Klein launches redone with a wider store / fp64 far field
+    uint64_t n_launch[4] = {};    // run_klein launches: exact, VALU, MFMA fp64, MFMA int8 (LGS_COUNTER_LAUNCH_*)
     // 32-row-panel kernels: the certificate's bound on sum_j |z_j| of a sample (an
     // estimate from the basis, then twice the largest sum seen; a sample exceeding it
     // is replayed in the reference's order, so the cap only affects speed)
@@ -638,6 +639,11 @@ int run_klein(lgs_ctx* c, lgs::KleinArgs& a, bool exact, bool wl, int zb, void* 
         a.h16_lanes = lanes;
         used_oz = true;
     }
+    const int launched = kernel == lgs::kKernelExact  ? LGS_COUNTER_LAUNCH_EXACT
+                         : kernel == lgs::kKernelValu ? LGS_COUNTER_LAUNCH_VALU
+                         : used_oz                    ? LGS_COUNTER_LAUNCH_MFMA_I8
+                                                      : LGS_COUNTER_LAUNCH_MFMA_FP64;
+    c->n_launch[launched - LGS_COUNTER_LAUNCH_EXACT] += 1;
     HIP_TRY(lgs::launch::klein(a, c->R.as<double>(), c->RP.as<double>(), c->RC.as<double>(),
                                c->panel, kernel, wl, zb, Z, c->stream));
     return LGS_OK;
@@ -2093,13 +2099,14 @@ int lgs_timing_get(lgs_ctx* c, int kernel, double* ms, int64_t* n) {
 
 int lgs_counter(lgs_ctx* c, int which, int reset, uint64_t* value) {
     if (!c) return fail(LGS_ERR_INVALID, "null context");
-    if (which < LGS_COUNTER_RESOLVED || which > LGS_COUNTER_DECODE_RESOLVED)
-        return fail(LGS_ERR_INVALID, "counter id 0..6");
+    if (which < LGS_COUNTER_RESOLVED || which > LGS_COUNTER_LAUNCH_MFMA_I8)
+        return fail(LGS_ERR_INVALID, "counter id 0..10");
     if (which == LGS_COUNTER_KLEIN_CUS) {
         if (value) *value = (uint64_t)c->kstream_cus;
         return LGS_OK;
     }
-    uint64_t& v = which == LGS_COUNTER_RESOLVED      ? c->n_resolved
+    uint64_t& v = which >= LGS_COUNTER_LAUNCH_EXACT  ? c->n_launch[which - LGS_COUNTER_LAUNCH_EXACT]
+                  : which == LGS_COUNTER_RESOLVED    ? c->n_resolved
                   : which == LGS_COUNTER_FALLBACK    ? c->n_fallback
                   : which == LGS_COUNTER_ACCEPT_RESOLVED ? c->n_accept_resolved
                   : which == LGS_COUNTER_WL_MISMATCH ? c->n_wl_mismatch

@@ -205,19 +205,20 @@ __device__ __noinline__ SampleZOut sample_z_table(double mu, double sig, int pre
         out.log_norm = 0.0;
         return out;
     }
-    if (linear_probs && exp(shift) == 0.0) {
-        // use_log_space=False: every probability underflows -> NaN -> the
-        // reference's ValueError fallback round(mean) (klein.py:176-179).
-        out.z = (int64_t)rint(mu);
-        out.log_norm = -INFINITY;
-        return out;
-    }
     const double flo = (double)lo;
     const int n = (int)(hi - lo) + 1;
     double S = 0.0;
     for (int k = 0; k < n; ++k) {
         const double t = ((flo + (double)k) - mu) / sig;
         S += exp(-0.5 * (t * t) - shift);
+    }
+    if (linear_probs && exp(shift) == 0.0) {
+        // use_log_space=False: every probability underflows -> NaN -> the
+        // reference's ValueError fallback round(mean) (klein.py:176-179).  The
+        // normaliser (Wang-Ling weights) stays the log-space one, as the oracle's.
+        out.z = (int64_t)rint(mu);
+        out.log_norm = want_log ? shift + log(S) : 0.0;
+        return out;
     }
     const double target = u * S;
     double C = 0.0, Cp = 0.0;
@@ -551,11 +552,6 @@ __device__ __forceinline__ bool sample_z_small(double mu, double sig, int precis
         out.log_norm = 0.0;
         return true;
     }
-    if (linear_probs && emax < -745.2) {  // every probability underflows: round(mean)
-        out.z = (int64_t)rint(mu);
-        out.log_norm = -INFINITY;
-        return true;
-    }
     double w[4];
     double S = 0.0;
 #pragma unroll
@@ -563,6 +559,11 @@ __device__ __forceinline__ bool sample_z_small(double mu, double sig, int precis
         const double x = e[k] - emax;
         w[k] = x == 0.0 ? 1.0 : (x < -745.2 ? 0.0 : exp(x));
         S += w[k];
+    }
+    if (linear_probs && emax < -745.2) {  // every probability underflows: round(mean);
+        out.z = (int64_t)rint(mu);        // the normaliser stays the log-space one (the oracle's)
+        out.log_norm = want_log ? emax + log(S) : 0.0;
+        return true;
     }
     const double target = u * S;
     double C = 0.0, Cp = 0.0, Cz = S;
@@ -1102,10 +1103,6 @@ __device__ __forceinline__ double sample_z_coord_body(double mu, double u, QP qi
                            : (want_log ? emax : 0.0);
             return kmax;
         }
-        if (linear_probs && emax < -745.2) {
-            log_norm = cert ? __builtin_nan("") : -INFINITY;
-            return rint(mu);
-        }
         double w[4];
         double Ssum = 0.0;
 #pragma unroll
@@ -1113,6 +1110,12 @@ __device__ __forceinline__ double sample_z_coord_body(double mu, double u, QP qi
             const double x = e[k] - emax;
             w[k] = x == 0.0 ? 1.0 : (x < -745.2 ? 0.0 : exp(x));
             Ssum += w[k];
+        }
+        if (linear_probs && emax < -745.2) {
+            // every probability underflows: the reference's fallback round(mean); the
+            // normaliser (Wang-Ling weights) stays the log-space one, as the oracle's
+            log_norm = cert ? __builtin_nan("") : (want_log ? emax + log(Ssum) : 0.0);
+            return rint(mu);
         }
         const double target = u * Ssum;
         double C = 0.0, z = hi, Cp = 0.0, Cz = Ssum;

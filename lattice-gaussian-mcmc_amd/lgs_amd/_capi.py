@@ -61,6 +61,11 @@ LGS_COUNTER_WL_MISMATCH = 3
 LGS_COUNTER_QSKIP = 4
 LGS_COUNTER_KLEIN_CUS = 5
 LGS_COUNTER_DECODE_RESOLVED = 6
+# Klein launches by the kernel run_klein chose (exact order, VALU, MFMA fp64 / int8-digit far field)
+LGS_COUNTER_LAUNCH_EXACT = 7
+LGS_COUNTER_LAUNCH_VALU = 8
+LGS_COUNTER_LAUNCH_MFMA_FP64 = 9
+LGS_COUNTER_LAUNCH_MFMA_I8 = 10
 
 # every symbol include/lgs.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = ("lgs_version", "lgs_last_error", "lgs_create", "lgs_create_ex", "lgs_destroy", "lgs_set_stream",

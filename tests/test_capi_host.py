@@ -197,6 +197,28 @@ def test_imhk_outputs_struct_matches_header():
     assert ctypes.sizeof(_capi.ImhkOutputs) == 8 * len(names)
 
 
+def test_counter_ids_match_header():
+    """Every LGS_COUNTER_* id of lgs.h has the same value in the ctypes binding, the ids
+    are 0..10 without gaps, the four launch counters follow LGS_COUNTER_DECODE_RESOLVED in
+    the order exact, VALU, MFMA fp64, MFMA int8, and lgs_counter's range check names the
+    same range."""
+    from lgs_amd import _capi
+    hdr = open(HEADER).read()
+    ids = {n: int(v) for n, v in re.findall(r"^#define (LGS_COUNTER_\w+)\s+(\d+)", hdr, re.M)}
+    assert sorted(ids.values()) == list(range(11))
+    for name, v in ids.items():
+        assert getattr(_capi, name) == v, name
+    assert [ids[f"LGS_COUNTER_LAUNCH_{k}"] for k in ("EXACT", "VALU", "MFMA_FP64", "MFMA_I8")] == \
+        [ids["LGS_COUNTER_DECODE_RESOLVED"] + k for k in (1, 2, 3, 4)]
+    src = open(os.path.join(REPO, "lattice-gaussian-mcmc_amd", "csrc", "lgs_capi.hip")).read()
+    body = src[src.index("int lgs_counter(lgs_ctx* c"):]
+    body = body[:body.index("\n}\n")]
+    assert "which > LGS_COUNTER_LAUNCH_MFMA_I8" in body and '"counter id 0..10"' in body
+    L = _capi.load_library()
+    v = ctypes.c_uint64(0)
+    assert L.lgs_counter(None, _capi.LGS_COUNTER_LAUNCH_MFMA_I8, 0, ctypes.byref(v)) == _capi.LGS_ERR_INVALID
+
+
 def test_compile_time_switches_are_the_listed_ones():
     """Every LGS_* name a preprocessor conditional of csrc/ tests is a switch in the list
     at the top of lgs_kernels.h or a macro csrc/ itself #defines, and every listed switch

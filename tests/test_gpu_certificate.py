@@ -174,7 +174,8 @@ def test_q_panel_skip_equals_full_computation(capi, oracle, cfg, center_scale, m
         ctx.klein(17, 3 << 20, n, z, None, lw, capi.LGS_DEVICE_PTRS | capi.LGS_COORD_MAJOR)
         ms, _ = ctx.timing_get(capi.KERNEL_KLEIN)
         out[skip] = (z, lw, ms, ctx.counter(capi.LGS_COUNTER_QSKIP))
-    ctx.klein(17, 3 << 20, n, out["1"][0], None, None, capi.LGS_DEVICE_PTRS | capi.LGS_COORD_MAJOR | capi.LGS_EXACT_ORDER)
+    ze = torch.empty((d, n), dtype=torch.int32, device="cuda")  # the reference-order kernel's, in its own tensor
+    ctx.klein(17, 3 << 20, n, ze, None, None, capi.LGS_DEVICE_PTRS | capi.LGS_COORD_MAJOR | capi.LGS_EXACT_ORDER)
     torch.cuda.synchronize()
     qs = out["0"][3]
     print(f"{cfg} center {center_scale}: skip {out['0'][2]:.3f} ms ({qs} wave-panels skipped), "
@@ -188,5 +189,6 @@ def test_q_panel_skip_equals_full_computation(capi, oracle, cfg, center_scale, m
     else:
         assert qs == 0
     assert torch.equal(out["0"][0], out["1"][0])  # skipped panels: the same z as computed ones
+    assert torch.equal(out["0"][0], ze)  # and as the reference-order kernel's
     rel = float(((out["0"][1] - out["1"][1]).abs() / out["1"][1].abs().clamp_min(1.0)).max())
     assert rel < 1e-12, rel

@@ -91,17 +91,27 @@ def _wide_sigma_basis(d, seed):
 @pytest.mark.parametrize("wl", [False, True])
 def test_klein_coord_constants_vs_generic_samplez(ctx, ctx_libm, oracle, capi, precision, wl):
     """Per-coordinate SampleZ constants (closed-form / fitted window normalisers)
-    give the generic path's decisions and log-weights, and the oracle's z."""
+    give the generic path's decisions and log-weights, and the oracle's z: in the VALU
+    panel kernel (n = 3000, a ragged launch) and in the MFMA kernel with the int8-digit
+    far field (n = 3072, whole 256-sample blocks)."""
     R, cp = _wide_sigma_basis(96, precision)
-    out = []
     flags = capi.LGS_WANG_LING if wl else 0
-    for c in (ctx, ctx_libm):
-        c.set_basis(R, cp, None, 10.0, precision=precision)
-        out.append(c.klein_host(99, 5, 3000, want_z=True, want_v=False, want_logw=True, flags=flags))
-    assert np.array_equal(out[0]["z"], out[1]["z"])
-    np.testing.assert_allclose(out[0]["logw"], out[1]["logw"], rtol=1e-12, atol=1e-9)
+    kinds = (capi.LGS_COUNTER_LAUNCH_EXACT, capi.LGS_COUNTER_LAUNCH_VALU, capi.LGS_COUNTER_LAUNCH_MFMA_FP64,
+             capi.LGS_COUNTER_LAUNCH_MFMA_I8)
     o = oracle.klein(R, cp, 10.0, 200, seed=99, first_sample=5, precision=precision)
-    assert np.array_equal(out[0]["z"][:200], o["z"])
+    for n, ran in ((3000, (0, 1, 0, 0)), (3072, (0, 0, 0, 1))):
+        out = []
+        for c in (ctx, ctx_libm):
+            c.set_basis(R, cp, None, 10.0, precision=precision)
+            for k in kinds:
+                c.counter(k, reset=True)
+            c.fallbacks(reset=True)
+            out.append(c.klein_host(99, 5, n, want_z=True, want_v=False, want_logw=True, flags=flags))
+            assert tuple(c.counter(k) for k in kinds) == ran  # the kernel this n is here for
+            assert c.fallbacks() == 0
+        assert np.array_equal(out[0]["z"], out[1]["z"])
+        np.testing.assert_allclose(out[0]["logw"], out[1]["logw"], rtol=1e-12, atol=1e-9)
+        assert np.array_equal(out[0]["z"][:200], o["z"])
 
 
 @pytest.fixture(scope="module")
@@ -205,14 +215,20 @@ def test_klein_batch_and_offset_invariance(ctx):
 
 
 def test_small_launch_chunks_and_panel16(capi, oracle):
-    """Chunked launches (max_proposals) and the 16-row panel give identical z."""
+    """Chunked launches (max_proposals) and the 16-row panel give identical z.  Every chunk
+    has at most 100 lanes, so this is the 16-row VALU panel kernel (the 16-row MFMA kernel:
+    test_gpu_kernel_matrix.py)."""
     g = load_golden("klein_qary128.npz")
     R, cp, B = golden_R(g)
     c2 = capi.Context(0, max_proposals=100, panel=16)
     c2.set_basis(R, cp, B, float(g["sigma"]))
-    r = c2.klein_host(int(g["seed"]), 0, int(g["n"]), want_z=True, want_v=True)
+    n = int(g["n"])
+    r = c2.klein_host(int(g["seed"]), 0, n, want_z=True, want_v=True)
     assert np.array_equal(r["z"], g["z"])
     assert np.array_equal(r["v"], g["v"])
+    assert c2.counter(capi.LGS_COUNTER_LAUNCH_VALU) == (n + 99) // 100  # one launch per chunk
+    assert c2.counter(capi.LGS_COUNTER_LAUNCH_EXACT) == c2.counter(capi.LGS_COUNTER_LAUNCH_MFMA_FP64) == \
+        c2.counter(capi.LGS_COUNTER_LAUNCH_MFMA_I8) == 0
 
 
 def test_overflow_falls_back_to_int64(ctx, capi):

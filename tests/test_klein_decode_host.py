@@ -25,7 +25,7 @@ def test_header_declares_klein_decode():
     c = re.search(r"^#define LGS_COUNTER_DECODE_RESOLVED\s+(\d+)", txt, re.M)
     assert c and int(c.group(1)) == 6
     ids = [int(v) for v in re.findall(r"^#define LGS_COUNTER_\w+\s+(\d+)", txt, re.M)]
-    assert sorted(ids) == list(range(7))  # no id shared or skipped
+    assert sorted(ids) == list(range(11))  # no id shared or skipped
 
 
 def test_library_exports_klein_decode():
