@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -15,6 +16,7 @@
 
 #include "../../include/lgs.h"
 #include "lgs_kernels.h"
+#include "lgs_qclean_host.h"
 #include "lgs_szc_host.h"
 
 namespace {
@@ -66,6 +68,9 @@ static size_t test_nomem_above() {  // (read per allocation: tests set and clear
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    // the allocation's serial number, never reused (an address can be: lgs::QKey names
+    // buffers by it)
+    uint64_t id = 0;
     ~DevBuf() {
         if (p) (void)hipFree(p);
     }
@@ -87,6 +92,8 @@ struct DevBuf {
             return fail(LGS_ERR_NOMEM, "hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
         }
         bytes = need;
+        static std::atomic<uint64_t> serial{0};  // (contexts may allocate from several threads)
+        id = ++serial;
         return LGS_OK;
     }
     void release() {  // (hipFree waits for the device's work on it)
@@ -143,6 +150,14 @@ struct lgs_ctx {
     bool has_qz2 = false;
     uint64_t n_accept_resolved = 0, n_wl_mismatch = 0;
     uint64_t n_qskip = 0;  // (wave, panel) pairs decided by the q-panel skip
+    uint64_t n_qskip_elided = 0;  // those that found their panel clean and stored nothing
+    // The q-panel skip's clean state of the working store (Z, H16, ZNZ): a byte per
+    // (wave, panel) kept by the Klein kernel (KleinArgs::qclean), and the key under
+    // which the host vouches for it (lgs_qclean_host.h).  Each pipelined buffer set
+    // has its own; both travel with the store (SetSwap).
+    DevBuf QCL;
+    lgs::QKey qkey;
+    uint64_t basis_gen = 0;  // counts lgs_set_basis calls (part of the key)
     uint64_t n_decode_resolved = 0;  // lgs_klein_decode: targets whose winner the bounds did not decide
     uint64_t n_fallback = 0;      // Klein launches redone with a wider store / fp64 far field
     uint64_t n_launch[4] = {};    // run_klein launches: exact, VALU, MFMA fp64, MFMA int8 (LGS_COUNTER_LAUNCH_*)
@@ -214,6 +229,8 @@ struct lgs_ctx {
     // stream after the set's last reader; the set's next Klein launch waits for it.
     struct BlockSet {
         DevBuf Z, LW, H16, ZNZ, CLIVE, flags;
+        DevBuf QCL;  // the set's clean state and its key (lgs_ctx::QCL)
+        lgs::QKey qkey;
         hipEvent_t ev_free = nullptr;
         bool free_recorded = false;
     } bset[3];
@@ -259,6 +276,13 @@ int check_ctx(lgs_ctx* c, bool need_basis = true) {
     return LGS_OK;
 }
 
+// Before any clearing of flag words: the clean-state keys that wait on one (a gated
+// launch's word, QKey::dirty_if) are void -- every store's, whichever is swapped in.
+void qclean_flags_cleared(lgs_ctx* c) {
+    lgs::qkey_flags_cleared(c->qkey);
+    for (auto& s : c->bset) lgs::qkey_flags_cleared(s.qkey);
+}
+
 hipEvent_t get_event(lgs_ctx* c) {
     if (!c->pool.empty()) {
         hipEvent_t e = c->pool.back();
@@ -296,6 +320,7 @@ int run_bz_fp64(lgs_ctx* c, const BzCall& b);
 void swap_buf(DevBuf& a, DevBuf& b) {
     std::swap(a.p, b.p);
     std::swap(a.bytes, b.bytes);
+    std::swap(a.id, b.id);
 }
 
 // A pipelined block's buffer set swapped into the context's working buffers (which
@@ -317,6 +342,8 @@ struct SetSwap {
         swap_buf(c->H16, s.H16);
         swap_buf(c->ZNZ, s.ZNZ);
         swap_buf(c->CLIVE, s.CLIVE);
+        swap_buf(c->QCL, s.QCL);
+        std::swap(c->qkey, s.qkey);
         store_in = !store_in;
     }
     void restore() {
@@ -373,6 +400,8 @@ static int split_decide(lgs_ctx* c) {
 int spec_discard(lgs_ctx* c) {
     if (!c->spec.valid) return LGS_OK;
     c->spec.valid = false;
+    lgs::qkey_drop(c->bset[c->spec.j].qkey);  // (a launch nobody accounts for wrote the set)
+    qclean_flags_cleared(c);
     HIP_TRY(hipStreamSynchronize(c->kstream));
     HIP_TRY(hipMemset(c->bset[c->spec.j].flags.p, 0, 4 * lgs::kFlagWords));
     // its launch timers do not count (the launch's work is thrown away)
@@ -477,11 +506,13 @@ int finish(lgs_ctx* c, const unsigned int* fw_known = nullptr, bool clear_all = 
         HIP_TRY(hipMemcpy(fw, c->flags.p, sizeof(fw), hipMemcpyDeviceToHost));
     const unsigned int f = fw[0];
     c->resolved_seen = 0;
+    qclean_flags_cleared(c);
     if (fw[1] || fw[2] || fw[3])
         fold_counters(c, fw);
     c->n_accept_resolved += fw[lgs::kFlagWordAcceptResolved];
     c->n_wl_mismatch += fw[lgs::kFlagWordWLMismatch];
     c->n_qskip += fw[lgs::kFlagWordQSkip];
+    c->n_qskip_elided += fw[lgs::kFlagWordQSkipElided];
     c->n_decode_resolved += fw[lgs::kFlagWordDecodeResolved];
     bool any = false;
     for (int k = 1; k < lgs::kFlagWords; ++k) any |= fw[k] != 0;
@@ -522,6 +553,7 @@ int finish_or_redo(lgs_ctx* c, bool oz_used, int& zb, bool& redo, bool early = f
         HIP_TRY(hipMemcpy(fw, c->flags.p, sizeof(fw), hipMemcpyDeviceToHost));
     }
     if (!(fw[0] & lgs::kAbortMask)) return finish(c, fw, early);
+    qclean_flags_cleared(c);
     c->pending_i8.clear();
     c->i8_dev_replay = false;
     for (auto& t : c->pending) {  // the aborted attempt's timers are not kept
@@ -545,6 +577,7 @@ int finish_or_redo(lgs_ctx* c, bool oz_used, int& zb, bool& redo, bool early = f
 int reset_flags(lgs_ctx* c) {
     int rc = c->flags.reserve(4 * lgs::kFlagWords);
     if (rc) return rc;
+    qclean_flags_cleared(c);
     c->resolved_seen = 0;
     HIP_TRY(hipMemsetAsync(c->flags.p, 0, 4 * lgs::kFlagWords, c->stream));
     return LGS_OK;
@@ -638,6 +671,47 @@ int run_klein(lgs_ctx* c, lgs::KleinArgs& a, bool exact, bool wl, int zb, void* 
         a.h16_shift = shift;
         a.h16_lanes = lanes;
         used_oz = true;
+    }
+    // The q-panel skip's clean state.  Every Klein launch from here writes the working
+    // H16 / ZNZ or Z, so it either claims the key (an int8-digit reference-mode launch
+    // into the working store: the kernel keeps the state in step with what it stores)
+    // or drops it.  A gated launch (lgs_imhk's initial draws) may return without writing
+    // anything, the state included, so it cannot claim; it leaves its device word with
+    // the key instead, and the next claiming launch resets itself if the word is set
+    // (the word is valid until the flag words are cleared: qclean_flags_cleared).  The
+    // other writers of these buffers drop the key
+    // where they write (qkey_drop); carry_cols writes only the columns >= npb of Z,
+    // which no lane of the block's launch owns, and neither H16 nor ZNZ.
+    a.qclean = nullptr;
+    a.qclean_reset = 0;
+    a.qclean_gate = nullptr;
+    const int64_t npan = (c->d + 31) / 32;
+    if (used_oz && !wl && a.qz2 && !a.gate && Z == c->Z.p && npan <= lgs::kQCleanPanels) {
+        const int rc = c->QCL.reserve(((size_t)(a.h16_lanes / 64) * npan + 3) / 4 * 4);
+        if (rc) return rc;
+        lgs::QKey k;
+        k.z_id = c->Z.id;
+        k.h16_id = c->H16.id;
+        k.znz_id = c->ZNZ.id;
+        k.state_id = c->QCL.id;
+        k.Z = Z;
+        k.H16 = a.h16;
+        k.ZNZ = a.znz;
+        k.ldz = a.ldz;
+        k.h16_lanes = a.h16_lanes;
+        k.n = a.n;
+        k.h16_shift = a.h16_shift;
+        k.d = a.d;
+        k.zb = zb;
+        k.counter_mode = a.counter_mode;
+        k.chain0 = a.chain0;
+        k.basis_gen = c->basis_gen;
+        a.qclean = c->QCL.as<uint8_t>();
+        a.qclean_reset = lgs::qkey_claim(c->qkey, k, &a.qclean_gate) ? 0 : 1;
+    } else if (a.gate && Z == c->Z.p) {
+        lgs::qkey_gated_write(c->qkey, a.gate);  // (writes if *gate != 0: the next launch checks)
+    } else {
+        lgs::qkey_drop(c->qkey);
     }
     const int launched = kernel == lgs::kKernelExact  ? LGS_COUNTER_LAUNCH_EXACT
                          : kernel == lgs::kKernelValu ? LGS_COUNTER_LAUNCH_VALU
@@ -982,6 +1056,10 @@ int lgs_set_basis(lgs_ctx* c, int64_t d, const double* R, const double* cprime, 
     // copies below are not ordered after a non-blocking stream's work
     HIP_TRY(hipStreamSynchronize(c->stream));
     if ((rc = spec_discard(c))) return rc;  // (a look-ahead launch reads the basis being replaced)
+    // another basis skips other panels: every store's clean state starts over
+    c->basis_gen += 1;
+    lgs::qkey_drop(c->qkey);
+    for (auto& s : c->bset) lgs::qkey_drop(s.qkey);
     if (c->kstream_split && c->cu_split != 0 && !hook("LGS_PIPE_CU_RESERVE")) {  // the CU split decided anew
         HIP_TRY(hipStreamSynchronize(c->kstream));
         c->kstream = c->kstream_full;
@@ -1429,6 +1507,7 @@ int lgs_lattice_points(lgs_ctx* c, int64_t n, const void* z, double* v_out, uint
         if (cm) {
             Zc = src;
         } else {
+            lgs::qkey_drop(c->qkey);
             HIP_TRY(lgs::launch::to_coord_major(src, zb, n, (int)d, c->Z.p, zb, n, c->stream));
             Zc = c->Z.p;
         }
@@ -1465,6 +1544,7 @@ int lgs_log_density(lgs_ctx* c, int64_t n, const void* z, double* out, uint32_t 
         if (cm) {
             Zc = src;
         } else {
+            lgs::qkey_drop(c->qkey);
             HIP_TRY(lgs::launch::to_coord_major(src, zb, n, (int)d, c->Z.p, zb, n, c->stream));
             Zc = c->Z.p;
         }
@@ -2117,6 +2197,13 @@ int lgs_counter(lgs_ctx* c, int which, int reset, uint64_t* value) {
     return LGS_OK;
 }
 
+int lgs_qskip_elided(lgs_ctx* c, int reset, uint64_t* value) {
+    if (!c) return fail(LGS_ERR_INVALID, "null context");
+    if (value) *value = c->n_qskip_elided;
+    if (reset) c->n_qskip_elided = 0;
+    return LGS_OK;
+}
+
 int lgs_device_info(lgs_ctx* c, char* name, int name_len, int* n_cu, int64_t* hbm) {
     int rc = check_ctx(c, false);
     if (rc) return rc;
@@ -2518,6 +2605,7 @@ int run_decode(lgs_ctx* c, bool plane, int64_t n, const double* targets, void* z
                                       c->stream));
         HIP_TRY(lgs::launch::to_coord_major(Y, 8, m, (int)d, X, 8, m, c->stream));
         void* Zp = c->Z.p;
+        lgs::qkey_drop(c->qkey);  // (written below by another kernel than the Klein launch that keeps it)
         if (plane) {
             const double* co = c->coord.as<double>();
             HIP_TRY(lgs::launch::nearest_plane((int)d, m, c->panel, c->RP.as<double>(), c->RC.as<double>(),
@@ -2668,6 +2756,7 @@ int lgs_klein_targets(lgs_ctx* c, uint64_t seed, uint64_t first, int64_t n, cons
         a.n = mp;
         a.ldz = mp;
         void* Zp = c->Z.p;
+        lgs::qkey_drop(c->qkey);  // (written below by another kernel than the Klein launch that keeps it)
         {
             Scope s(c, 0);
             c->hist.Z = nullptr;  // (no int16 history: B z reads the store)
@@ -2797,6 +2886,7 @@ int lgs_klein_decode(lgs_ctx* c, uint64_t seed, uint64_t first, int64_t n, int64
         a.n = mp;
         a.ldz = mp;
         void* Zp = c->Z.p;
+        lgs::qkey_drop(c->qkey);  // (written below by another kernel than the Klein launch that keeps it)
         const lgs::DecodeLanes dl{K, c->DEC_D.as<double>(), c->DEC_E.as<double>()};
         {
             Scope s(c, 0);

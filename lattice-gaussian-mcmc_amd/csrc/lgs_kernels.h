@@ -172,7 +172,20 @@ struct KleinArgs {
     // 64-coordinate chunk c (zeroed before the launch; B z's chunk skipping)
     unsigned int* clive;
     int64_t clive_ld;
+    // q-panel skip, clean state (nullable; with qz2 and h16, at most kQCleanPanels 32-row
+    // panels; a multiple of 4 bytes, 4-byte aligned): byte qclean[wave * npan + pk], wave
+    // = p / 64 of the launch, nonzero when that wave's Z rows, history blocks and znz
+    // bytes of panel pk hold the skip's values (0, z + 128 = 0x0080, 0) since its last
+    // launch into the same buffers.  A wave that skips such a panel stores nothing.
+    // Each byte is read and written only by the wave that owns it.  qclean_reset != 0:
+    // the bytes are not read (every panel counts as dirty) and all are rewritten;
+    // qclean_gate (nullable): the same when *qclean_gate != 0 (the device word that
+    // gated a launch into the store since: lgs_imhk's initial draws).
+    uint8_t* qclean;
+    int qclean_reset;
+    const unsigned int* qclean_gate;
 };
+constexpr int kQCleanPanels = 128;  // d <= 4096
 
 // Counter / check words of the context's flag buffer used by the certified
 // Wang-Ling accept decisions (imhk_accept_kernel)
@@ -180,7 +193,8 @@ constexpr int kFlagWordAcceptResolved = 6;  // decisions redone at reference-ord
 constexpr int kFlagWordWLMismatch = 7;      // recomputed draws that did not reproduce the stored z (a bug)
 constexpr int kFlagWordQSkip = 8;           // (wave, panel) pairs of the q-panel skip (klein_mfma_kernel)
 constexpr int kFlagWordDecodeResolved = 9;  // lgs_klein_decode: targets whose winner the bounds did not decide
-constexpr int kFlagWords = 16;              // the flag buffer: 64 bytes
+constexpr int kFlagWordQSkipElided = 10;    // those whose stores were elided (KleinArgs::qclean)
+constexpr int kFlagWords = 16;             // the flag buffer: 64 bytes
 
 // Per-lane outputs of the decode sampling kernels (lgs_klein_decode): K draws per
 // target, lane p = t K + k; D[p] the draw's squared distance to its target as the kernel

@@ -1022,6 +1022,13 @@ __device__ __forceinline__ void oz_far_field(const KleinArgs& a, int pk, int p_h
 #endif
 }
 
+// The q-panel skip's clean state starts over: by the host's flag or the device word
+// of a gated launch that wrote the store since (KleinArgs::qclean_gate)
+__device__ __forceinline__ bool qclean_reset(const KleinArgs& a) {
+    return a.qclean_reset != 0 ||
+           (a.qclean_gate != nullptr && *(const __attribute__((address_space(4))) unsigned int*)a.qclean_gate != 0u);
+}
+
 // Diagnostic builds (-DLGS_DIAG_CYCLES): per-wave shader-clock accounting of the
 // 32-row-panel kernel, summed over waves into lgs_diag_cycles (lane 0 adds):
 // [0] record staging + barriers, [1] far field, [2] near field, [3 + kind] the
@@ -1040,7 +1047,11 @@ __device__ unsigned long long lgs_diag_cycles[16];
 constexpr int kOzLB = 2, kMfmaLB32 = 3;
 // OZ (32-row panels only): far field as an exact int8-digit product on
 // v_mfma_i32_16x16x64_i8 instead of fp64 MFMA (see oz_far_field).
-template <typename ZT, int PB, bool WL, bool OZ = false, bool LIBM = false>
+// QC (OZ, reference mode): the q-panel skip keeps its clean state (KleinArgs::qclean != nullptr).
+// An instantiation of its own: the state's few scalar registers cost spills in a kernel that
+// already spills, and a launch without state (a basis that never skips, C4) must run the code
+// it ran before.
+template <typename ZT, int PB, bool WL, bool OZ = false, bool LIBM = false, bool QC = false>
 __global__ __launch_bounds__(256, PB == 32 ? (OZ ? kOzLB : kMfmaLB32) : 3) void klein_mfma_kernel(const KleinArgs a,
                                                             const double* __restrict__ RP,
                                                             const double* __restrict__ RC,
@@ -1063,6 +1074,12 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? kOzLB : kMfmaLB32) : 3) void 
     __shared__ __attribute__((aligned(16))) double rec_lds[PB == 32 ? 32 * kRecStride : 2];
     // OZ: bit q set when panel q has a nonzero coefficient in some sample of the block
     __shared__ uint32_t nzm[OZ ? kOzMaxD / 32 / 32 : 1];
+    static_assert(!QC || (OZ && !WL && PB == 32), "clean state: int8-digit far field, reference mode");
+    // QC: each wave's count of skipped panels whose stores were elided (zeroed here; the
+    // first use lies behind the first panel's barrier)
+    __shared__ uint32_t qcnt[QC ? 4 : 1];
+    if constexpr (QC)
+        if (threadIdx.x < 4) qcnt[threadIdx.x] = 0u;
     if constexpr (OZ)
         for (int e = threadIdx.x; e < kOzMaxD / 32 / 32; e += 256) nzm[e] = 0u;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1126,6 +1143,14 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? kOzLB : kMfmaLB32) : 3) void 
             // (round 6) each wave votes before the barrier that ends the previous panel; a
             // panel the block skips stages no records (the weight terms are read from the
             // record array in memory) and needs no second barrier
+            // Clean state (a.qclean, one byte per wave of the launch and panel): nonzero
+            // when this wave's Z rows, history blocks and znz bytes of the panel hold the
+            // skip's values (0, 0x0080, 0) since the wave's last launch into the same
+            // buffers, which the host vouches for (lgs_capi.hip QKey).  A skip of such a
+            // panel stores nothing.  The byte is read once, in the skip itself (a scalar
+            // load in the batch of the weight terms' loads; no register lives across
+            // panels), and written only by its wave: 1 by a skip that stored, 0 by a
+            // panel decided the normal way.
             if (qtry) {
                 const double q2 = ((const __attribute__((address_space(4))) double*)a.qz2)[pk];
                 const bool ok = __builtin_amdgcn_ballot_w64(active && !(qzs[threadIdx.x] <= q2)) == 0;
@@ -1149,12 +1174,29 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? kOzLB : kMfmaLB32) : 3) void 
                 // scalar loads), added in the sequential order
                 const cdptr lt = uniformize(cst(a.lterm) + r0);
                 double ltv[32];
+                if constexpr (QC) {
+                    uint32_t qcw = 0u;  // the aligned word that holds this panel's byte
+                    const uint32_t qi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(p0 >> 6)) * (uint32_t)npan + pk;
+                    if (!qclean_reset(a)) qcw = ((const __attribute__((address_space(4))) uint32_t*)a.qclean)[qi >> 2];
 #pragma unroll
-                for (int s = 0; s < 32; ++s) ltv[s] = lt[31 - s];
+                    for (int s = 0; s < 32; ++s) ltv[s] = lt[31 - s];
 #pragma unroll
-                for (int s = 0; s < 32; ++s) {
-                    Z[(size_t)(p_hi - 1 - s) * ldz + p] = (ZT)0;
-                    lw += ltv[s];
+                    for (int s = 0; s < 32; ++s) lw += ltv[s];
+                    if (((qcw >> (8 * (qi & 3))) & 0xffu) != 0u) {  // clean: every value below is already there
+                        if (lane == 0) qcnt[wave] += 1u;
+                        continue;
+                    }
+                    if (lane == 0) a.qclean[qi] = 1;
+#pragma unroll
+                    for (int s = 0; s < 32; ++s) Z[(size_t)(p_hi - 1 - s) * ldz + p] = (ZT)0;
+                } else {
+#pragma unroll
+                    for (int s = 0; s < 32; ++s) ltv[s] = lt[31 - s];
+#pragma unroll
+                    for (int s = 0; s < 32; ++s) {
+                        Z[(size_t)(p_hi - 1 - s) * ldz + p] = (ZT)0;
+                        lw += ltv[s];
+                    }
                 }
                 v4u_t* hp4 = (v4u_t*)(a.h16 + ((size_t)((p_hi - 32 + a.h16_shift) >> 4) * a.h16_lanes + p) * 16);
                 const v4u_t h128 = (v4u_t){0x00800080u, 0x00800080u, 0x00800080u, 0x00800080u};
@@ -1167,6 +1209,11 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? kOzLB : kMfmaLB32) : 3) void 
                     a.znz[(size_t)((p_hi - 16 + a.h16_shift) >> 4) * a.h16_lanes + p] = 0;
                 }
                 continue;
+            }
+            // decided the normal way: the panel's values are this launch's (a panel the
+            // loaded basis never skips keeps the 0 that a reset launch wrote)
+            if constexpr (QC) {
+                if ((qtry || qclean_reset(a)) && lane == 0) a.qclean[(uint32_t)(p0 >> 6) * (uint32_t)npan + pk] = 0;
             }
         }
         // Coarse panel (reference mode, both sub-panels speculative): the far field with
@@ -1599,6 +1646,9 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? kOzLB : kMfmaLB32) : 3) void 
         if (lane == 0) atomicMax(a.emax, (unsigned long long)__double_as_longlong(m));
     }
     if (!active) return;
+    if constexpr (QC) {
+        if (lane == 0 && qcnt[wave] != 0u) atomicAdd(a.flags + kFlagWordQSkipElided, qcnt[wave]);
+    }
     if (a.LW) a.LW[p] = lw;
     if (WL && PB == 32 && a.LWE) a.LWE[p] = ewl;
     if (WL && PB != 32) wl_bound_store(a, p, ewl);
@@ -3392,7 +3442,13 @@ static void klein_pb(const KleinArgs& a, const double* RP, const double* RC, int
         if (PB == 32 && a.rd) {  // int8-digit far field
             if (libm && wl)
                 hipLaunchKernelGGL((klein_mfma_kernel<ZT, PB, true, true, true>), grid, dim3(256), 0, st, a, RP, RC, z);
-            else if (libm)
+            else if (PB == 32 && a.qclean && !wl) {  // (the skip's clean state: its own instantiation)
+                constexpr bool QC = PB == 32;
+                if (libm)
+                    hipLaunchKernelGGL((klein_mfma_kernel<ZT, PB, false, true, true, QC>), grid, dim3(256), 0, st, a, RP, RC, z);
+                else
+                    hipLaunchKernelGGL((klein_mfma_kernel<ZT, PB, false, true, false, QC>), grid, dim3(256), 0, st, a, RP, RC, z);
+            } else if (libm)
                 hipLaunchKernelGGL((klein_mfma_kernel<ZT, PB, false, true, true>), grid, dim3(256), 0, st, a, RP, RC, z);
             else if (wl)
                 hipLaunchKernelGGL((klein_mfma_kernel<ZT, PB, true, true>), grid, dim3(256), 0, st, a, RP, RC, z);

@@ -72,7 +72,7 @@ EXPORTS = ("lgs_version", "lgs_last_error", "lgs_create", "lgs_create_ex", "lgs_
            "lgs_set_basis", "lgs_klein", "lgs_imhk", "lgs_imhk_trace", "lgs_imhk_ex", "lgs_lattice_points", "lgs_log_density", "lgs_sample_z", "lgs_timing_enable",
            "lgs_timing_get", "lgs_device_info", "lgs_series_stats", "lgs_gram",
            "lgs_jump_distance", "lgs_marginal_tvd", "lgs_column_range", "lgs_histogram", "lgs_set_decoder", "lgs_nearest_plane",
-           "lgs_round_decode", "lgs_counter", "lgs_klein_targets", "lgs_klein_decode")
+           "lgs_round_decode", "lgs_counter", "lgs_qskip_elided", "lgs_klein_targets", "lgs_klein_decode")
 
 
 class ImhkOutputs(ctypes.Structure):
@@ -149,6 +149,7 @@ def load_library(path: str = LIB_PATH):
     L.lgs_timing_enable.argtypes = [_vp, ctypes.c_int]
     L.lgs_timing_get.argtypes = [_vp, ctypes.c_int, _dp, _i64p]
     L.lgs_counter.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
+    L.lgs_qskip_elided.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
     L.lgs_device_info.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                   _i64p]
     _i64 = ctypes.c_int64
@@ -606,6 +607,13 @@ class Context:
         """lgs_counter: one of the LGS_COUNTER_* event counts since creation / the last reset."""
         v = ctypes.c_uint64(0)
         self._ck(self._L.lgs_counter(self._h, int(which), 1 if reset else 0, ctypes.byref(v)))
+        return v.value
+
+    def qskip_elided(self, reset=False):
+        """lgs_qskip_elided: the q-panel skips (LGS_COUNTER_QSKIP) that found their panel clean
+        and stored nothing."""
+        v = ctypes.c_uint64(0)
+        self._ck(self._L.lgs_qskip_elided(self._h, 1 if reset else 0, ctypes.byref(v)))
         return v.value
 
     def device_info(self):
