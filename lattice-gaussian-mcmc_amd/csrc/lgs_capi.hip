@@ -1390,6 +1390,10 @@ int lgs_set_basis(lgs_ctx* c, int64_t d, const double* R, const double* cprime, 
         c->has_Bi8 = false;
     }
     c->d = d;
+    // the decoding frame (Q, B^-1) belonged to the basis replaced: lgs_set_decoder uploads
+    // the new one (the buffers stay, it re-reserves them)
+    c->has_q = false;
+    c->has_binv = false;
     c->sigma = sigma;
     c->precision = precision;
     c->basis_flags = flags;
@@ -2576,7 +2580,10 @@ int run_decode(lgs_ctx* c, bool plane, int64_t n, const double* targets, void* z
     const int64_t d = c->d;
     const int ob = z64 ? 8 : 4;
     if ((rc = reset_flags(c))) return rc;
-    const int64_t chunk = std::min<int64_t>(n, std::max<int64_t>(256, ((int64_t)1 << 27) / d));
+    int64_t chunk = std::min<int64_t>(n, std::max<int64_t>(256, ((int64_t)1 << 27) / d));
+    // (hooks build) LGS_TEST_DECODE_CHUNK=m: chunks of m targets, so that tests reach the
+    // second chunk's offsets at small n (read per call: tests set and clear it)
+    if (const char* s = hook("LGS_TEST_DECODE_CHUNK")) chunk = std::min<int64_t>(n, std::max<int64_t>(1, atoll(s)));
     if ((rc = c->dg_x.reserve((size_t)chunk * d * 8)) || (rc = c->dg_y.reserve((size_t)chunk * d * 8)) ||
         (rc = c->Z.reserve((size_t)chunk * d * ob)))
         return rc;

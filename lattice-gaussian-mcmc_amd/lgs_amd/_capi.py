@@ -405,9 +405,22 @@ class Context:
         self._keep_dec = (Qc, Bi)
 
     def decode(self, targets, method="plane", z_out=None, v_out=None, flags=0):
-        """Raw lgs_nearest_plane / lgs_round_decode on caller buffers."""
+        """Raw lgs_nearest_plane / lgs_round_decode on caller buffers (numpy host or device
+        tensors).  targets is float64 (n, d), or (d, n) with LGS_COORD_MAJOR; z_out has the
+        same layout, int32 or int64 per LGS_Z64; v_out is float64 (n, d)."""
+        if method not in ("plane", "round"):
+            raise ValueError("method is 'plane' or 'round'")
+        cm = bool(flags & LGS_COORD_MAJOR)
+        if len(targets.shape) != 2 or targets.shape[0 if cm else 1] != self.d:
+            raise ValueError(f"targets must be (n, {self.d}), or ({self.d}, n) with LGS_COORD_MAJOR")
+        n = targets.shape[1] if cm else targets.shape[0]
+        zt = "int64" if flags & LGS_Z64 else "int32"
+        _check_bufs(flags, self.device, ((targets, "float64", "targets"), (z_out, zt, "z_out"),
+                                         (v_out, "float64", "v_out")))
+        for a, want, name in ((z_out, (self.d, n) if cm else (n, self.d), "z_out"), (v_out, (n, self.d), "v_out")):
+            if a is not None and not isinstance(a, int) and tuple(a.shape) != want:
+                raise ValueError(f"{name}: expected shape {want}, got {tuple(a.shape)}")
         fn = self._L.lgs_nearest_plane if method == "plane" else self._L.lgs_round_decode
-        n = targets.shape[1] if flags & LGS_COORD_MAJOR else targets.shape[0]
         self._ck(fn(self._h, int(n), _ptr(targets), _ptr(z_out), _ptr(v_out), int(flags)))
 
     def decode_host(self, targets, method="plane", want_v=True):
