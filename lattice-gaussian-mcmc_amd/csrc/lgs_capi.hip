@@ -214,6 +214,10 @@ struct lgs_ctx {
     // lgs_klein_decode: per-lane distance and bound, winners' columns / draw index / distance,
     // the winners' compact coordinate-major store
     DevBuf DEC_D, DEC_E, DEC_WIN, DEC_BEST, DEC_D2, DEC_Z;
+    // lgs_imhk_targets (with host pointers): the chunk's per-chain log weight, accept count,
+    // final step and accepted trace (its per-draw weights and bounds: LW, LWE; its final
+    // columns and compact store: DEC_WIN, DEC_Z)
+    DevBuf IT_LOGW, IT_ACC, IT_STEP, IT_TRACE;
     bool has_q = false, has_binv = false;
     std::vector<Timer> pending;
     std::vector<hipEvent_t> pool;
@@ -2685,6 +2689,50 @@ int lgs_round_decode(lgs_ctx* c, int64_t n, const double* targets, void* z_out, 
     return run_decode(c, false, n, targets, z_out, v_out, flags);
 }
 
+}  // extern "C"
+
+namespace {
+
+// The c' stage of the per-target samplers (timer 7): the centres of targets off .. off + m - 1
+// of the call's n, coordinate-major into X (ld >= m columns, those from m on zeroed) --
+// c' = Q^T t on fp64 MFMA, or the caller's c' itself with qframe.  Scratch: stage_a (host
+// targets), dg_x / dg_y (lattice frame), reserved by the caller for its chunk.
+int stage_centres(lgs_ctx* c, const double* targets, int64_t n, int64_t off, int64_t m, double* X, int64_t ld,
+                  bool dev, bool cm, bool qframe) {
+    const int64_t d = c->d;
+    Scope s(c, 7);
+    if (ld > m) HIP_TRY(hipMemset2DAsync(X + m, (size_t)ld * 8, 0, (size_t)(ld - m) * 8, (size_t)d, c->stream));
+    if (qframe && cm) {
+        HIP_TRY(hipMemcpy2DAsync(X, (size_t)ld * 8, targets + off, (size_t)n * 8, (size_t)m * 8, (size_t)d,
+                                 kind_of(true, dev), c->stream));
+        return LGS_OK;
+    }
+    const double* src;  // row-major m x d on the device
+    if (cm) {           // lattice frame, coordinate-major: T (d x m) for the GEMM
+        HIP_TRY(hipMemcpy2DAsync(c->dg_x.p, (size_t)m * 8, targets + off, (size_t)n * 8, (size_t)m * 8, (size_t)d,
+                                 kind_of(true, dev), c->stream));
+        src = nullptr;
+    } else {
+        src = targets + (size_t)off * d;
+        if (!dev) {
+            HIP_TRY(hipMemcpyAsync(c->stage_a.p, src, (size_t)m * d * 8, hipMemcpyHostToDevice, c->stream));
+            src = c->stage_a.as<double>();
+        }
+        if (!qframe) HIP_TRY(lgs::launch::to_coord_major(src, 8, m, (int)d, c->dg_x.p, 8, m, c->stream));
+    }
+    if (!qframe) {
+        HIP_TRY(lgs::launch::gemm_f64(c->dg_x.as<double>(), m, c->DQ.as<double>(), (int)d, m, c->dg_y.as<double>(),
+                                      c->stream));
+        src = c->dg_y.as<double>();
+    }
+    HIP_TRY(lgs::launch::to_coord_major(src, 8, m, (int)d, X, 8, ld, c->stream));
+    return LGS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 // Klein draws around one centre per sample.  Per chunk of max_proposals targets: the
 // centres c' = Q^T t (or the caller's c') coordinate-major in CPT, padded with zeros to
 // whole waves (m -> mp lanes, timer 7); the draw into a coefficient store of the output
@@ -2729,34 +2777,7 @@ int lgs_klein_targets(lgs_ctx* c, uint64_t seed, uint64_t first, int64_t n, cons
     for (int64_t off = 0; off < n; off += chunk) {
         const int64_t m = std::min<int64_t>(chunk, n - off);
         const int64_t mp = (m + 63) / 64 * 64;
-        {
-            Scope s(c, 7);
-            if (mp > m) HIP_TRY(hipMemset2DAsync(X + m, (size_t)mp * 8, 0, (size_t)(mp - m) * 8, (size_t)d, c->stream));
-            if (qframe && cm) {
-                HIP_TRY(hipMemcpy2DAsync(X, (size_t)mp * 8, targets + off, (size_t)n * 8, (size_t)m * 8, (size_t)d,
-                                         kind_of(true, dev), c->stream));
-            } else {
-                const double* src;  // row-major m x d on the device
-                if (cm) {           // lattice frame, coordinate-major: T (d x m) for the GEMM
-                    HIP_TRY(hipMemcpy2DAsync(c->dg_x.p, (size_t)m * 8, targets + off, (size_t)n * 8, (size_t)m * 8,
-                                             (size_t)d, kind_of(true, dev), c->stream));
-                    src = nullptr;
-                } else {
-                    src = targets + (size_t)off * d;
-                    if (!dev) {
-                        HIP_TRY(hipMemcpyAsync(c->stage_a.p, src, (size_t)m * d * 8, hipMemcpyHostToDevice, c->stream));
-                        src = c->stage_a.as<double>();
-                    }
-                    if (!qframe) HIP_TRY(lgs::launch::to_coord_major(src, 8, m, (int)d, c->dg_x.p, 8, m, c->stream));
-                }
-                if (!qframe) {
-                    HIP_TRY(lgs::launch::gemm_f64(c->dg_x.as<double>(), m, c->DQ.as<double>(), (int)d, m,
-                                                  c->dg_y.as<double>(), c->stream));
-                    src = c->dg_y.as<double>();
-                }
-                HIP_TRY(lgs::launch::to_coord_major(src, 8, m, (int)d, X, 8, mp, c->stream));
-            }
-        }
+        if ((rc = stage_centres(c, targets, n, off, m, X, mp, dev, cm, qframe))) return rc;
         lgs::KleinArgs a = base_args(c, seed);
         a.counter_mode = 0;
         a.base = first + (uint64_t)off;
@@ -2859,34 +2880,7 @@ int lgs_klein_decode(lgs_ctx* c, uint64_t seed, uint64_t first, int64_t n, int64
     for (int64_t off = 0; off < n; off += chunk) {
         const int64_t m = std::min<int64_t>(chunk, n - off);
         const int64_t mp = (m * K + 63) / 64 * 64;
-        {
-            Scope s(c, 7);
-            if (ldc > m) HIP_TRY(hipMemset2DAsync(X + m, (size_t)ldc * 8, 0, (size_t)(ldc - m) * 8, (size_t)d, c->stream));
-            if (qframe && cm) {
-                HIP_TRY(hipMemcpy2DAsync(X, (size_t)ldc * 8, targets + off, (size_t)n * 8, (size_t)m * 8, (size_t)d,
-                                         kind_of(true, dev), c->stream));
-            } else {
-                const double* src;  // row-major m x d on the device
-                if (cm) {           // lattice frame, coordinate-major: T (d x m) for the GEMM
-                    HIP_TRY(hipMemcpy2DAsync(c->dg_x.p, (size_t)m * 8, targets + off, (size_t)n * 8, (size_t)m * 8,
-                                             (size_t)d, kind_of(true, dev), c->stream));
-                    src = nullptr;
-                } else {
-                    src = targets + (size_t)off * d;
-                    if (!dev) {
-                        HIP_TRY(hipMemcpyAsync(c->stage_a.p, src, (size_t)m * d * 8, hipMemcpyHostToDevice, c->stream));
-                        src = c->stage_a.as<double>();
-                    }
-                    if (!qframe) HIP_TRY(lgs::launch::to_coord_major(src, 8, m, (int)d, c->dg_x.p, 8, m, c->stream));
-                }
-                if (!qframe) {
-                    HIP_TRY(lgs::launch::gemm_f64(c->dg_x.as<double>(), m, c->DQ.as<double>(), (int)d, m,
-                                                  c->dg_y.as<double>(), c->stream));
-                    src = c->dg_y.as<double>();
-                }
-                HIP_TRY(lgs::launch::to_coord_major(src, 8, m, (int)d, X, 8, ldc, c->stream));
-            }
-        }
+        if ((rc = stage_centres(c, targets, n, off, m, X, ldc, dev, cm, qframe))) return rc;
         lgs::KleinArgs a = base_args(c, seed);
         a.counter_mode = 0;
         a.base = first + (uint64_t)off * (uint64_t)K;
@@ -2931,6 +2925,165 @@ int lgs_klein_decode(lgs_ctx* c, uint64_t seed, uint64_t first, int64_t n, int64
         if (o.bound_draws)
             HIP_TRY(hipMemcpyAsync(o.bound_draws + (size_t)off * K, dl.E, (size_t)m * K * 8, kind_of(dev, true),
                                    c->stream));
+        if (cprime_out) {  // row-major, the centres the kernel read
+            void* dst = dev ? (void*)(cprime_out + (size_t)off * d) : c->stage_b.p;
+            HIP_TRY(lgs::launch::transpose_out(X, 8, ldc, m, (int)d, dst, 8, c->stream));
+            if (!dev)
+                HIP_TRY(hipMemcpyAsync(cprime_out + (size_t)off * d, dst, (size_t)m * d * 8, hipMemcpyDeviceToHost,
+                                       c->stream));
+        }
+        if (v_out) {
+            double* V = dev ? v_out + (size_t)off * d : c->V.as<double>();
+            if ((rc = run_bz(c, Wp, ob, ldw, m, V))) return rc;
+            if ((rc = settle_bz(c))) return rc;
+            if (!dev)
+                HIP_TRY(hipMemcpyAsync(v_out + (size_t)off * d, V, (size_t)m * d * 8, hipMemcpyDeviceToHost,
+                                       c->stream));
+        }
+        if ((rc = finish(c))) return rc;
+    }
+    return finish(c);
+}
+
+// IMHK chains around per-target centres: lgs_klein_decode with "the closest of K draws"
+// replaced by the Metropolis scan over K = n_steps + 1 draws.  Per chunk of
+// max_proposals / K chains: the centres once per target into CPT (timer 7); the draws of
+// lanes p = k K + t on the counters (chain first_chain + k, step t), padded to whole
+// waves, with each lane's Wang-Ling log weight and bound (timer 0); the certified scan, one
+// wave per chain, and the gather of the final states into the compact store and the
+// caller's layout (timer 8); B z of the m final states.  The n K x d store stays internal.
+int lgs_imhk_targets(lgs_ctx* c, uint64_t seed, uint64_t first_chain, int64_t n, int64_t n_steps,
+                     const double* targets, void* z_out, double* v_out, double* cprime_out,
+                     const lgs_imhk_targets_outputs* out, uint32_t flags) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (flags & ~(uint32_t)(LGS_DEVICE_PTRS | LGS_Z64 | LGS_COORD_MAJOR | LGS_EXACT_ORDER | LGS_TARGETS_QFRAME))
+        return fail(LGS_ERR_INVALID, "lgs_imhk_targets: unsupported flag 0x%x", flags);
+    if (n < 0) return fail(LGS_ERR_INVALID, "n < 0");
+    if (n_steps < 0 || n_steps >= c->max_props)
+        return fail(LGS_ERR_INVALID, "n_steps must be 0..max_proposals - 1 (%lld)", (long long)c->max_props - 1);
+    if (first_chain > (1ull << 32) || (uint64_t)n > (1ull << 32) - first_chain)
+        return fail(LGS_ERR_INVALID, "first_chain + n exceeds 2^32 (the chain counter has 32 bits)");
+    if (n == 0) return LGS_OK;
+    if (!targets) return fail(LGS_ERR_INVALID, "null targets");
+    const bool dev = flags & LGS_DEVICE_PTRS, z64 = flags & LGS_Z64, cm = flags & LGS_COORD_MAJOR,
+               exact = flags & LGS_EXACT_ORDER, qframe = flags & LGS_TARGETS_QFRAME;
+    if (!qframe && (!c->has_q || c->DQ.bytes < (size_t)c->d * c->d * 8))
+        return fail(LGS_ERR_STATE, "targets in the lattice frame need Q (lgs_set_decoder)");
+    if (v_out && !c->has_B) return fail(LGS_ERR_STATE, "v_out requires B");
+    const lgs_imhk_targets_outputs none{};
+    const lgs_imhk_targets_outputs& o = out ? *out : none;
+    const int64_t d = c->d, K = n_steps + 1;
+    const int ob = z64 ? 8 : 4;
+    if ((rc = reset_flags(c))) return rc;
+    const int64_t chunk = std::min<int64_t>(n, c->max_props / K);
+    const int64_t lanes_p = (chunk * K + 63) / 64 * 64;
+    const int64_t ldc = (lanes_p + K - 1) / K;  // >= chunk: the centre columns the lanes read
+    const int64_t ldw = (chunk + 63) / 64 * 64;
+    if ((rc = c->CPT.reserve((size_t)ldc * d * 8)) || (rc = c->Z.reserve((size_t)lanes_p * d * ob)) ||
+        (rc = c->LW.reserve((size_t)lanes_p * 8)) || (rc = c->LWE.reserve((size_t)lanes_p * 8)) ||
+        (rc = c->DEC_WIN.reserve((size_t)chunk * 8)) || (rc = c->DEC_Z.reserve((size_t)ldw * d * ob)))
+        return rc;
+    if (!qframe && ((rc = c->dg_x.reserve((size_t)chunk * d * 8)) || (rc = c->dg_y.reserve((size_t)chunk * d * 8))))
+        return rc;
+    if (!dev) {
+        if ((rc = c->stage_a.reserve((size_t)chunk * d * 8))) return rc;
+        if (cprime_out && (rc = c->stage_b.reserve((size_t)chunk * d * 8))) return rc;
+        if (v_out && (rc = c->V.reserve((size_t)chunk * d * 8))) return rc;
+        if ((o.logw && (rc = c->IT_LOGW.reserve((size_t)chunk * 8))) ||
+            (o.accepts && (rc = c->IT_ACC.reserve((size_t)chunk * 8))) ||
+            (o.final_step && (rc = c->IT_STEP.reserve((size_t)chunk * 8))) ||
+            (o.accepted && (rc = c->IT_TRACE.reserve((size_t)chunk * n_steps))))
+            return rc;
+    }
+    double dmu_scale = 1.0;
+    // test hook (as lgs_klein_decode): a scale s < 1 widens every certificate bound, and
+    // with it every weight bound, by 1 / s
+    if (const char* s = hook("LGS_TEST_Z1CAP_SCALE")) {
+        const double v = atof(s);
+        if (v > 0.0 && v < 1.0) dmu_scale = 1.0 / v;
+    }
+    // test hook (as lgs_imhk): widened weight bounds force the recomputation path on many
+    // decisions (clamped to >= 1: a smaller scale would void the certificate)
+    const char* bs = hook("LGS_TEST_WL_BOUND_SCALE");
+    const double bscale = bs ? std::max(1.0, atof(bs)) : 1.0;
+    double* X = c->CPT.as<double>();
+    for (int64_t off = 0; off < n; off += chunk) {
+        const int64_t m = std::min<int64_t>(chunk, n - off);
+        const int64_t mp = (m * K + 63) / 64 * 64;
+        if ((rc = stage_centres(c, targets, n, off, m, X, ldc, dev, cm, qframe))) return rc;
+        lgs::KleinArgs a = base_args(c, seed);
+        a.counter_mode = 1;
+        a.chain0 = (uint32_t)(first_chain + (uint64_t)off);
+        a.step0 = 0;
+        a.nt = K;
+        a.n = mp;
+        a.ldz = mp;
+        a.LW = c->LW.as<double>();
+        a.LWE = c->LWE.as<double>();
+        void* Zp = c->Z.p;
+        lgs::qkey_drop(c->qkey);  // (written below by another kernel than the Klein launch that keeps it)
+        {
+            Scope s(c, 0);
+            c->hist.Z = nullptr;  // (no int16 history: B z reads the compact store)
+            HIP_TRY(lgs::launch::klein_imhk_targets(a, c->R.as<double>(), c->RP.as<double>(), c->RC.as<double>(),
+                                                    c->panel, exact, X, ldc, dmu_scale, ob, Zp, lgs::WeightLanes{K},
+                                                    c->stream));
+        }
+        // the sampling kernel's weights and bounds, before the scan replaces recomputed ones
+        if (o.logw_draws)
+            HIP_TRY(hipMemcpyAsync(o.logw_draws + (size_t)off * K, a.LW, (size_t)m * K * 8, kind_of(dev, true),
+                                   c->stream));
+        if (o.bound_draws)
+            HIP_TRY(hipMemcpyAsync(o.bound_draws + (size_t)off * K, a.LWE, (size_t)m * K * 8, kind_of(dev, true),
+                                   c->stream));
+        lgs::ImhkTargetsArgs aa{};
+        aa.nc = m;
+        aa.K = K;
+        aa.seed = seed;
+        aa.chain0 = a.chain0;
+        aa.LW = a.LW;
+        aa.LWE = a.LWE;
+        aa.RT = c->RT.as<double>();
+        aa.Zst = Zp;
+        aa.zb = ob;
+        aa.ldz = mp;
+        aa.CP = X;
+        aa.ldc = ldc;
+        aa.final_col = c->DEC_WIN.as<int64_t>();
+        aa.logw = !o.logw ? nullptr : dev ? o.logw + off : c->IT_LOGW.as<double>();
+        aa.accepts = !o.accepts ? nullptr : dev ? o.accepts + off : c->IT_ACC.as<int64_t>();
+        aa.final_step = !o.final_step ? nullptr : dev ? o.final_step + off : c->IT_STEP.as<int64_t>();
+        aa.accepted = !o.accepted || n_steps == 0 ? nullptr
+                      : dev                       ? o.accepted + (size_t)off * n_steps
+                                                  : c->IT_TRACE.as<uint8_t>();
+        aa.flagw = c->flags.as<unsigned int>();
+        aa.bscale = bscale;
+        void* Wp = c->DEC_Z.p;
+        {
+            Scope s(c, 8);
+            HIP_TRY(lgs::launch::imhk_targets_accept(aa, a, c->stream));
+            void* zrow = nullptr;  // row-major final states: the caller's device buffer, or staged
+            if (z_out && !cm) zrow = dev ? (char*)z_out + (size_t)off * d * ob : c->stage_a.p;
+            HIP_TRY(lgs::launch::decode_gather((int)d, m, aa.final_col, Zp, ob, mp, Wp, ldw, zrow, d, 1, c->stream));
+            if (z_out && cm)
+                HIP_TRY(hipMemcpy2DAsync((char*)z_out + (size_t)off * ob, (size_t)n * ob, Wp, (size_t)ldw * ob,
+                                         (size_t)m * ob, (size_t)d, kind_of(dev, true), c->stream));
+            else if (z_out && !dev)
+                HIP_TRY(hipMemcpyAsync((char*)z_out + (size_t)off * d * ob, zrow, (size_t)m * d * ob,
+                                       hipMemcpyDeviceToHost, c->stream));
+        }
+        if (!dev) {
+            if (aa.logw) HIP_TRY(hipMemcpyAsync(o.logw + off, aa.logw, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
+            if (aa.accepts)
+                HIP_TRY(hipMemcpyAsync(o.accepts + off, aa.accepts, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
+            if (aa.final_step)
+                HIP_TRY(hipMemcpyAsync(o.final_step + off, aa.final_step, (size_t)m * 8, hipMemcpyDeviceToHost,
+                                       c->stream));
+            if (aa.accepted)
+                HIP_TRY(hipMemcpyAsync(o.accepted + (size_t)off * n_steps, aa.accepted, (size_t)m * n_steps,
+                                       hipMemcpyDeviceToHost, c->stream));
+        }
         if (cprime_out) {  // row-major, the centres the kernel read
             void* dst = dev ? (void*)(cprime_out + (size_t)off * d) : c->stage_b.p;
             HIP_TRY(lgs::launch::transpose_out(X, 8, ldc, m, (int)d, dst, 8, c->stream));

@@ -205,6 +205,37 @@ struct DecodeLanes {
     double* E;
 };
 
+// The sampling kernels of lgs_imhk_targets: K = n_steps + 1 draws per target, lane
+// p = k K + t (counter_mode 1, nt = K).  The lanes' Wang-Ling log weights and their
+// bounds go to KleinArgs::LW / LWE (both non-null).
+struct WeightLanes {
+    int64_t K;
+};
+
+// The Metropolis scan of lgs_imhk_targets (imhk_targets_accept_kernel): chain k < nc
+// owns the draws of columns k K .. k K + K - 1, draw 0 its initial state.
+struct ImhkTargetsArgs {
+    int64_t nc;
+    int64_t K;
+    uint64_t seed;
+    uint32_t chain0;
+    double* LW;             // per draw: log weight (recomputed ones are written back)
+    double* LWE;            // per draw: E >= |LW - reference-order log weight| (then 0)
+    const double* RT;       // R transposed, d x d
+    const void* Zst;        // the draws (coordinate-major, column p, ld ldz, zb-byte elements)
+    int zb;
+    int64_t ldz;
+    const double* CP;       // the chains' centres, coordinate-major: CP[i * ldc + k]
+    int64_t ldc;
+    int64_t* final_col;     // nc: the column of the chain's final state
+    double* logw;           // nullable, nc: its log weight
+    int64_t* accepts;       // nullable, nc: accepted proposals (overwritten)
+    int64_t* final_step;    // nullable, nc: its counter step
+    uint8_t* accepted;      // nullable, nc x (K - 1)
+    unsigned int* flagw;    // the context's flag words (kFlagWordAcceptResolved, kFlagWordWLMismatch)
+    double bscale;          // bounds x bscale (1; a test hook widens them to force recomputations)
+};
+
 struct AcceptArgs {
     int64_t nc;
     int64_t T;
@@ -404,6 +435,15 @@ hipError_t klein_targets(const KleinArgs& a, const double* R, const double* RP, 
 hipError_t klein_decode(const KleinArgs& a, const double* R, const double* RP, const double* RC, int panel,
                         bool exact, const double* CP, int64_t ldc, double dmu_scale, int zb, void* Z,
                         const DecodeLanes& dl, hipStream_t st);
+// lgs_imhk_targets: klein_decode's lanes and centres with the counters of counter_mode 1
+// (a.nt = wl.K) and Wang-Ling weights: a.LW[p] the lane's log weight as the kernel formed
+// it, a.LWE[p] >= |a.LW[p] - reference-order weight| (0 with exact).
+hipError_t klein_imhk_targets(const KleinArgs& a, const double* R, const double* RP, const double* RC, int panel,
+                              bool exact, const double* CP, int64_t ldc, double dmu_scale, int zb, void* Z,
+                              const WeightLanes& wl, hipStream_t st);
+// The certified Metropolis scan over each chain's K draws, a wave per chain (ka: the
+// sampling launch's arguments, for the weights recomputed in the reference's order)
+hipError_t imhk_targets_accept(const ImhkTargetsArgs& a, const KleinArgs& ka, hipStream_t st);
 // Per target t < m: the draw of columns t K .. t K + K - 1 with the smallest
 // reference-order distance, ties to the smallest k.  Candidates are the draws whose interval
 // [D - E, D + E] reaches below min_k (D_k + E_k); a single candidate wins, several are

@@ -1670,18 +1670,23 @@ __global__ __launch_bounds__(256, PB == 32 ? (OZ ? kOzLB : kMfmaLB32) : 3) void 
 
 // resolve_coord with the lane's own centre: the decision of coordinate i redone at
 // the reference-order mean (c'_i - sum_{j>i} R_ij z_j) / R_ii, same uniform.
-template <typename ZT>
+// WL (lgs_imhk_targets): the Wang-Ling term at that mean, as resolve_coord<WL> above.
+template <bool WL = false, typename ZT>
 __device__ __forceinline__ double resolve_coord(const KleinArgs& a, int i, double cpl, const ZT* Zp, size_t ldz,
-                                                CoordStream& rs, unsigned int& flags) {
+                                                CoordStream& rs, unsigned int& flags, double& lw, double& tb) {
     const size_t iq = (size_t)i * kSzcStride;
     const Resolved r = resolve_decision(a.R, Zp, ldz, i, a.d, cpl, cst(a.rii)[i],
                                         a.szc ? a.szc + iq : nullptr,
                                         a.szc ? cst(a.szc)[iq] : cst(a.sig)[i], rs.u((uint32_t)(a.d - 1 - i)),
-                                        a.precision, a.linear_probs != 0, false, a.etab,
+                                        a.precision, a.linear_probs != 0, WL, a.etab,
                                         a.flags + kFlagWordResolved);
     if (!isfinite(r.mu)) {
         flags |= kFlagNonFinite;
         return 0.0;
+    }
+    if (WL) {
+        lw += r.ln;
+        tb += fabs(r.ln);  // (a term at the reference-order mean: no bound)
     }
     return r.z;
 }
@@ -1694,7 +1699,12 @@ __device__ __forceinline__ double resolve_coord(const KleinArgs& a, int i, doubl
 // ||t - B z||^2 = sum_i r_i^2 with r_i = (c'_i - cs_i) - R_ii z_i (Q is square), see
 // DecodeLanes in lgs_kernels.h.  Here cs is the reference-order sum, so D is the
 // reference-order distance itself and the bound is 0.
-template <typename ZT, bool DEC>
+//
+// WL (lgs_imhk_targets): K = n_steps + 1 draws per target, lane p = k K + t with the
+// counters (chain0 + k, step t) of counter_mode 1; the lane returns its Wang-Ling log
+// weight, the sum of the window log normalisers at these means (decide_coord<true>, what
+// klein_exact_kernel<ZT, true> returns at the context's centre), in a.LW with bound 0.
+template <typename ZT, bool DEC, bool WL = false>
 __device__ __forceinline__ void klein_targets_exact_body(const KleinArgs& a, const double* __restrict__ R,
                                                          const double* __restrict__ CP, int64_t ldc,
                                                          ZT* __restrict__ Z, const DecodeLanes& dl) {
@@ -1702,7 +1712,7 @@ __device__ __forceinline__ void klein_targets_exact_body(const KleinArgs& a, con
     const lds_cdptr etab_s = stage_etab(tab_lds, a.etab);
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= a.n) return;
-    const double* __restrict__ cpp = CP + (DEC ? p / dl.K : p);
+    const double* __restrict__ cpp = CP + (DEC || WL ? p / dl.K : p);
     double D = 0.0;
     uint32_t chain, step;
     lane_counter(a, p, chain, step);
@@ -1718,7 +1728,7 @@ __device__ __forceinline__ void klein_targets_exact_body(const KleinArgs& a, con
         double cs = 0.0;
         for (int j = i + 1; j < d; ++j) cs = cs + Ri[j] * (double)Z[(size_t)j * ldz + p];
         const double mu = (cpl - cs) / a.rii[i];
-        const double zi = decide_coord<false>(a, i, mu, rs, lw, flags, etab_s, -1.0, eb, tb);
+        const double zi = decide_coord<WL>(a, i, mu, rs, lw, flags, etab_s, -1.0, eb, tb);
         store_z(Z, (size_t)i * ldz + p, zi, flags);
         if (DEC) {
             const double q = Ri[i] * zi;
@@ -1730,6 +1740,11 @@ __device__ __forceinline__ void klein_targets_exact_body(const KleinArgs& a, con
         if (!isfinite(D)) flags |= kFlagNonFinite;
         dl.D[p] = D;
         dl.E[p] = 0.0;
+    }
+    if (WL) {
+        if (!isfinite(lw)) flags |= kFlagNonFinite;
+        a.LW[p] = lw;
+        a.LWE[p] = 0.0;  // the reference's order: exact
     }
     if (flags) atomicOr(a.flags, flags);
 }
@@ -1748,6 +1763,14 @@ __global__ __launch_bounds__(256) void klein_decode_exact_kernel(const KleinArgs
                                                                  const double* __restrict__ CP, int64_t ldc,
                                                                  ZT* __restrict__ Z, const DecodeLanes dl) {
     klein_targets_exact_body<ZT, true>(a, R, CP, ldc, Z, dl);
+}
+
+template <typename ZT>
+__global__ __launch_bounds__(256) void klein_imhk_exact_kernel(const KleinArgs a,
+                                                               const double* __restrict__ R,
+                                                               const double* __restrict__ CP, int64_t ldc,
+                                                               ZT* __restrict__ Z, const WeightLanes wl) {
+    klein_targets_exact_body<ZT, false, true>(a, R, CP, ldc, Z, DecodeLanes{wl.K, nullptr, nullptr});
 }
 
 // Blocked, certified: the panel layout of klein_panel_kernel (RP / RC, PB = 16 or 32
@@ -1778,8 +1801,17 @@ __global__ __launch_bounds__(256) void klein_decode_exact_kernel(const KleinArgs
 // A decision redone in the reference order changes z_i, not how rt_i was formed.
 // The decode instantiation is klein_targets_kernel<ZT, PB, DecodeLanes> with the lanes'
 // outputs as a trailing argument; without it the kernel is lgs_klein_targets' own.
+//
+// WL (lgs_imhk_targets): klein_targets_kernel<ZT, PB, WeightLanes>.  The lane's centre is
+// column p / K, its counters those of counter_mode 1 with nt = K, and decide_coord<true>
+// adds each coordinate's Wang-Ling term at the blocked-order mean with the term's bound
+// at the certificate's dmu (wl_bound_generic); a decision redone in the reference order
+// adds its term at the reference-order mean, which has no bound.  The lane writes
+// a.LW[p] and a.LWE[p] = wl_bound_sum(eb, tb, d) >= |LW - reference-order weight|, as
+// klein_panel_kernel<ZT, PB, true> does at the context's centre.
 __device__ __forceinline__ DecodeLanes decode_lanes() { return DecodeLanes{1, nullptr, nullptr}; }
 __device__ __forceinline__ DecodeLanes decode_lanes(const DecodeLanes& dl) { return dl; }
+__device__ __forceinline__ DecodeLanes decode_lanes(const WeightLanes& wl) { return DecodeLanes{wl.K, nullptr, nullptr}; }
 
 template <typename ZT, int PB, typename... DL>
 __global__ __launch_bounds__(256) void klein_targets_kernel(const KleinArgs a,
@@ -1787,7 +1819,7 @@ __global__ __launch_bounds__(256) void klein_targets_kernel(const KleinArgs a,
                                                             const double* __restrict__ RC,
                                                             const double* __restrict__ CP, int64_t ldc,
                                                             double dmu_scale, ZT* __restrict__ Z, const DL... dls) {
-    constexpr bool DEC = sizeof...(DL) != 0;
+    constexpr bool DEC = (std::is_same<DL, DecodeLanes>::value || ...), WL = (std::is_same<DL, WeightLanes>::value || ...);
     constexpr int NT = PB / 16, LDF = 65;
     __shared__ double Fl[4][16 * LDF];
     __shared__ double tab_lds[2 * (kErfTabLast + 1)];
@@ -1808,7 +1840,7 @@ __global__ __launch_bounds__(256) void klein_targets_kernel(const KleinArgs a,
     double* F = Fl[wave];
     const int kq = lane >> 4, nq = lane & 15;
     const DecodeLanes dl = decode_lanes(dls...);
-    const double* __restrict__ cpp = CP + (DEC ? p / dl.K : p);
+    const double* __restrict__ cpp = CP + (DEC || WL ? p / dl.K : p);
     double acc[16];
     double z1 = 0.0;
     double Dt = 0.0, At = 0.0;
@@ -1895,10 +1927,10 @@ __global__ __launch_bounds__(256) void klein_targets_kernel(const KleinArgs a,
                 if (i > 0) cpl = cpp[(size_t)(i - 1) * ldc];  // the next coordinate's centre, in flight
                 double dmu = 0.0;
                 if constexpr (DEC) dmu = cert_dmu(cst(a.cert)[2 * i], cst(a.cert)[2 * i + 1], z1, mu) * dmu_scale;
-                double zi = decide_coord<false>(a, i, mu, rs, lw, flags, etab_s,
-                                                cert_dmu(cst(a.cert)[2 * i], cst(a.cert)[2 * i + 1], z1, mu) * dmu_scale,
-                                                eb, tb);
-                if (zi == kAmbiguous) zi = resolve_coord(a, i, cpi, Z + p, ldz, rs, flags);
+                double zi = decide_coord<WL>(a, i, mu, rs, lw, flags, etab_s,
+                                             cert_dmu(cst(a.cert)[2 * i], cst(a.cert)[2 * i + 1], z1, mu) * dmu_scale,
+                                             eb, tb);
+                if (zi == kAmbiguous) zi = resolve_coord<WL>(a, i, cpi, Z + p, ldz, rs, flags, lw, tb);
                 z1 += fabs(zi);
                 store_z(Z, (size_t)i * ldz + p, zi, flags);
                 if constexpr (DEC) {
@@ -1924,6 +1956,12 @@ __global__ __launch_bounds__(256) void klein_targets_kernel(const KleinArgs a,
         if (!isfinite(Dt) || !isfinite(E)) flags |= kFlagNonFinite;
         dl.D[p] = Dt;
         dl.E[p] = E;
+    }
+    if constexpr (WL) {
+        const double E = wl_bound_sum(eb, tb, d);
+        if (!isfinite(lw) || !isfinite(E)) flags |= kFlagNonFinite;
+        a.LW[p] = lw;
+        a.LWE[p] = E;
     }
     if (flags) atomicOr(a.flags, flags);
 }
@@ -2267,9 +2305,12 @@ __device__ __forceinline__ double wl_decide_lane(const KleinArgs& a, int i, doub
 // (16 per pass, so d > 1024 takes several passes, top rows first); z_j is broadcast
 // (zero terms skipped: cs + R * (+-0) = cs, cs is never -0), R is read through its
 // transpose (one coalesced row segment per m).  z_j at zsrc[j * zst], width zb.
+// c'_i at cp[i * cps]: the context's centre (a.cp, 1) or the sample's own column of
+// per-target centres (lgs_imhk_targets).
 // check: the draws at those means must reproduce z (the sample's own counters).
-__device__ double wl_exact_wave(const KleinArgs& a, const double* __restrict__ RT, const void* zsrc, int zb,
-                                int64_t zst, uint32_t step, uint32_t chain, bool check, int& bad) {
+__device__ double wl_exact_wave(const KleinArgs& a, const double* __restrict__ RT, const double* __restrict__ cp,
+                                int64_t cps, const void* zsrc, int zb, int64_t zst, uint32_t step, uint32_t chain,
+                                bool check, int& bad) {
     const int lane = threadIdx.x & 63;
     const int d = a.d;
     constexpr int MB = 16;
@@ -2301,7 +2342,7 @@ __device__ double wl_exact_wave(const KleinArgs& a, const double* __restrict__ R
             const int i = ilo + 64 * m + lane;
             lnv[m] = 0.0;
             if (i < d) {
-                const double mu = (a.cp[i] - cs[m]) / a.rii[i];
+                const double mu = (cp[(size_t)i * cps] - cs[m]) / a.rii[i];
                 const double zi = wl_decide_lane(a, i, mu, rs.u((uint32_t)(d - 1 - i)), lnv[m]);
                 if (check && zi != zload(zsrc, zb, (int64_t)i * zst)) bad = 1;
             }
@@ -2376,14 +2417,14 @@ __global__ __launch_bounds__(64) void imhk_accept_cert_kernel(const AcceptArgs a
             double ly = 0.0, lx = 0.0;
             int badx = 0;  // (the carried state's replay did not reproduce its z)
             if (eyL != 0.0)
-                ly = wl_exact_wave(ka, a.RT, (const char*)a.Zst + (cL * a.T + t) * a.zb, a.zb, a.ldz,
+                ly = wl_exact_wave(ka, a.RT, ka.cp, 1, (const char*)a.Zst + (cL * a.T + t) * a.zb, a.zb, a.ldz,
                                    a.step0 + (uint32_t)t, chL, true, bad);
             if (exL != 0.0) {
                 if (curL >= 0)  // an earlier proposal of this block
-                    lx = wl_exact_wave(ka, a.RT, (const char*)a.Zst + curL * a.zb, a.zb, a.ldz,
+                    lx = wl_exact_wave(ka, a.RT, ka.cp, 1, (const char*)a.Zst + curL * a.zb, a.zb, a.ldz,
                                        a.step0 + (uint32_t)(curL % a.T), chL, true, bad);
                 else  // the state carried in: replayed at its own step when state_init has it
-                    lx = wl_exact_wave(ka, a.RT,
+                    lx = wl_exact_wave(ka, a.RT, ka.cp, 1,
                                        (const char*)a.zs + (a.zs_cm ? cL : cL * ka.d) * a.ob, a.ob,
                                        a.zs_cm ? a.nc : 1,
                                        sinitL >= kInitStep0 ? (uint32_t)(sinitL - kInitStep0) : 0u, chL,
@@ -2442,6 +2483,76 @@ __global__ __launch_bounds__(64) void imhk_accept_cert_kernel(const AcceptArgs a
     a.final_sel[c] = cur;
     if (a.cnt_carry) a.cnt_carry[c] = carry;
     if (a.state_init && cur >= 0) a.state_init[c] = init_code(a.step0 + (uint32_t)(cur % a.T));
+}
+
+// The scan of lgs_imhk_targets: imhk_accept_cert_kernel without carried state.  Chain
+// c owns the draws of columns c K .. c K + K - 1 around its own centre (column c of CP);
+// its state starts at draw 0 and step t = 1 .. K - 1 takes draw t iff
+// u_t < min(1, exp(lw_t - lw_x)), u_t = accept_uniform(seed, t, chain0 + c).  Every state
+// is a draw of this launch, so a weight whose bound left a decision open is recomputed
+// with the draw's own counters and centre, and comes back with bound 0.
+// One wave per chain, every lane carrying the chain's state: the recomputation needs the
+// whole wave, a chain's open decisions come one after the other, and on bases with a
+// wide certificate they are not rare (with 64 chains per wave the call waited
+// for the wave with the most of them).  Lane 0 writes.
+__global__ __launch_bounds__(64) void imhk_targets_accept_kernel(const ImhkTargetsArgs a, const KleinArgs ka) {
+    const int lane = threadIdx.x & 63;
+    const int64_t K = a.K;
+    unsigned int nres = 0;
+    int bad = 0;
+    for (int64_t c = blockIdx.x; c < a.nc; c += gridDim.x) {
+        const uint32_t chain = a.chain0 + (uint32_t)c;
+        const double* __restrict__ cpc = a.CP + c;
+        int64_t cur = c * K;
+        double lw_x = a.LW[cur];
+        double e_x = a.bscale * a.LWE[cur];
+        int64_t acc = 0;
+        for (int64_t t = 1; t < K; ++t) {
+            const int64_t p = c * K + t;
+            double lw_y = a.LW[p];
+            double e_y = a.bscale * a.LWE[p];
+            const double u = accept_uniform(a.seed, (uint32_t)t, chain);
+            bool take = false;
+            const bool sure = accept_certain(lw_x, e_x, lw_y, e_y, u, take);
+            if (__builtin_amdgcn_ballot_w64(!sure) != 0) {  // (the same on every lane) reference-order weights
+                if (e_y != 0.0) {
+                    lw_y = wl_exact_wave(ka, a.RT, cpc, a.ldc, (const char*)a.Zst + p * a.zb, a.zb, a.ldz,
+                                         (uint32_t)t, chain, true, bad);
+                    e_y = 0.0;
+                    if (lane == 0) {
+                        a.LW[p] = lw_y;
+                        a.LWE[p] = 0.0;
+                    }
+                }
+                if (e_x != 0.0) {
+                    lw_x = wl_exact_wave(ka, a.RT, cpc, a.ldc, (const char*)a.Zst + cur * a.zb, a.zb, a.ldz,
+                                         (uint32_t)(cur - c * K), chain, true, bad);
+                    e_x = 0.0;
+                    if (lane == 0) {
+                        a.LW[cur] = lw_x;
+                        a.LWE[cur] = 0.0;
+                    }
+                }
+                take = u < accept_ratio(lw_y, lw_x);
+                ++nres;
+            }
+            if (take) {
+                cur = p;
+                lw_x = lw_y;
+                e_x = e_y;
+                ++acc;
+            }
+            if (a.accepted && lane == 0) a.accepted[c * (K - 1) + (t - 1)] = take ? 1 : 0;
+        }
+        if (lane == 0) {
+            a.final_col[c] = cur;
+            if (a.logw) a.logw[c] = lw_x;
+            if (a.accepts) a.accepts[c] = acc;
+            if (a.final_step) a.final_step[c] = cur - c * K;
+        }
+    }
+    if (nres && lane == 0) atomicAdd(a.flagw + kFlagWordAcceptResolved, nres);
+    if (__builtin_amdgcn_ballot_w64(bad != 0) != 0 && lane == 0) atomicAdd(a.flagw + kFlagWordWLMismatch, 1u);
 }
 
 // ------------------------------------------------------------ moments
@@ -3734,6 +3845,40 @@ hipError_t klein_decode(const KleinArgs& a, const double* R, const double* RP, c
         hipLaunchKernelGGL((klein_targets_kernel<int32_t, 32, DecodeLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int32_t*)Z, dl);
     else
         hipLaunchKernelGGL((klein_targets_kernel<int64_t, 32, DecodeLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int64_t*)Z, dl);
+    return hipGetLastError();
+}
+
+hipError_t klein_imhk_targets(const KleinArgs& a, const double* R, const double* RP, const double* RC, int panel,
+                              bool exact, const double* CP, int64_t ldc, double dmu_scale, int zb, void* Z,
+                              const WeightLanes& wl, hipStream_t st) {
+    if (a.n <= 0) return hipSuccess;
+    if ((zb != 4 && zb != 8) || wl.K < 1 || !a.LW || !a.LWE || a.counter_mode != 1 || a.nt != wl.K)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((a.n + 255) / 256));
+    if (exact) {
+        if (zb == 4)
+            hipLaunchKernelGGL(klein_imhk_exact_kernel<int32_t>, grid, dim3(256), 0, st, a, R, CP, ldc, (int32_t*)Z, wl);
+        else
+            hipLaunchKernelGGL(klein_imhk_exact_kernel<int64_t>, grid, dim3(256), 0, st, a, R, CP, ldc, (int64_t*)Z, wl);
+        return hipGetLastError();
+    }
+    if (a.n % 64 != 0 || a.ldz % 4 != 0 || ((uintptr_t)Z % 16) != 0) return hipErrorInvalidValue;
+    if (panel == 16 && zb == 4)
+        hipLaunchKernelGGL((klein_targets_kernel<int32_t, 16, WeightLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int32_t*)Z, wl);
+    else if (panel == 16)
+        hipLaunchKernelGGL((klein_targets_kernel<int64_t, 16, WeightLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int64_t*)Z, wl);
+    else if (zb == 4)
+        hipLaunchKernelGGL((klein_targets_kernel<int32_t, 32, WeightLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int32_t*)Z, wl);
+    else
+        hipLaunchKernelGGL((klein_targets_kernel<int64_t, 32, WeightLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int64_t*)Z, wl);
+    return hipGetLastError();
+}
+
+hipError_t imhk_targets_accept(const ImhkTargetsArgs& a, const KleinArgs& ka, hipStream_t st) {
+    if (a.nc <= 0) return hipSuccess;
+    if ((a.zb != 4 && a.zb != 8) || a.K < 1 || !a.LW || !a.LWE || !a.final_col) return hipErrorInvalidValue;
+    const int64_t blocks = a.nc < ((int64_t)1 << 20) ? a.nc : (int64_t)1 << 20;  // a wave per chain (grid-stride beyond)
+    hipLaunchKernelGGL(imhk_targets_accept_kernel, dim3((unsigned)blocks), dim3(64), 0, st, a, ka);
     return hipGetLastError();
 }
 

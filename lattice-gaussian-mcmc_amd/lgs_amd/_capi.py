@@ -53,7 +53,7 @@ LGS_CTX_NO_CU_SPLIT = 0x80
 KERNEL_KLEIN, KERNEL_BZ, KERNEL_ACCEPT, KERNEL_MOMENTS = 0, 1, 2, 3
 KERNEL_GRAM, KERNEL_SERIES, KERNEL_KLEIN_INIT = 4, 5, 6
 KERNEL_CPRIME = 7  # lgs_klein_targets: the c' = Q^T t stage (transposes + GEMM)
-KERNEL_DECODE_SELECT = 8  # lgs_klein_decode: the select and gather launches
+KERNEL_DECODE_SELECT = 8  # lgs_klein_decode: the select and gather launches; lgs_imhk_targets: scan and gather
 LGS_COUNTER_RESOLVED = 0
 LGS_COUNTER_FALLBACK = 1
 LGS_COUNTER_ACCEPT_RESOLVED = 2
@@ -72,7 +72,8 @@ EXPORTS = ("lgs_version", "lgs_last_error", "lgs_create", "lgs_create_ex", "lgs_
            "lgs_set_basis", "lgs_klein", "lgs_imhk", "lgs_imhk_trace", "lgs_imhk_ex", "lgs_lattice_points", "lgs_log_density", "lgs_sample_z", "lgs_timing_enable",
            "lgs_timing_get", "lgs_device_info", "lgs_series_stats", "lgs_gram",
            "lgs_jump_distance", "lgs_marginal_tvd", "lgs_column_range", "lgs_histogram", "lgs_set_decoder", "lgs_nearest_plane",
-           "lgs_round_decode", "lgs_counter", "lgs_qskip_elided", "lgs_klein_targets", "lgs_klein_decode")
+           "lgs_round_decode", "lgs_counter", "lgs_qskip_elided", "lgs_klein_targets", "lgs_klein_decode",
+           "lgs_imhk_targets")
 
 
 class ImhkOutputs(ctypes.Structure):
@@ -88,6 +89,12 @@ class DecodeOutputs(ctypes.Structure):
     """struct lgs_decode_outputs (include/lgs.h)."""
     _fields_ = [("best_draw", ctypes.c_void_p), ("dist2", ctypes.c_void_p),
                 ("dist2_draws", ctypes.c_void_p), ("bound_draws", ctypes.c_void_p)]
+
+
+class ImhkTargetsOutputs(ctypes.Structure):
+    """struct lgs_imhk_targets_outputs (include/lgs.h)."""
+    _fields_ = [("logw", ctypes.c_void_p), ("accepts", ctypes.c_void_p), ("final_step", ctypes.c_void_p),
+                ("accepted", ctypes.c_void_p), ("logw_draws", ctypes.c_void_p), ("bound_draws", ctypes.c_void_p)]
 
 
 class LgsError(RuntimeError):
@@ -169,6 +176,9 @@ def load_library(path: str = LIB_PATH):
     if hasattr(L, "lgs_klein_decode"):  # (older A/B baselines lack it)
         L.lgs_klein_decode.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, _i64, _i64, _vp, _vp, _vp, _vp,
                                        ctypes.POINTER(DecodeOutputs), ctypes.c_uint32]
+    if hasattr(L, "lgs_imhk_targets"):  # (older A/B baselines lack it)
+        L.lgs_imhk_targets.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, _i64, _i64, _vp, _vp, _vp, _vp,
+                                       ctypes.POINTER(ImhkTargetsOutputs), ctypes.c_uint32]
     for name in EXPORTS:
         if name not in ("lgs_version", "lgs_last_error") and hasattr(L, name):
             getattr(L, name).restype = ctypes.c_int
@@ -536,6 +546,70 @@ class Context:
                  "best_draw": best, "dist2": d2}
             if want_draws:
                 r["dist2_draws"], r["bound_draws"] = dd, bd
+            return r
+        raise AssertionError("unreachable")
+
+    # ---------------------------------------------------------------- IMHK around per-target centres
+    def imhk_targets(self, seed, first_chain, targets, n_steps, z_out=None, v_out=None, cprime_out=None,
+                     logw=None, accepts=None, final_step=None, accepted=None, logw_draws=None,
+                     bound_draws=None, flags=0):
+        """Raw lgs_imhk_targets on caller buffers (numpy host or device tensors): one IMHK chain
+        of n_steps steps with Wang-Ling weights around each target; target k is chain
+        first_chain + k, its draw t on the counters (chain, step t).  targets as in
+        klein_targets; logw (n,) float64, accepts / final_step (n,) int64, accepted
+        (n, n_steps) uint8, logw_draws / bound_draws (n, n_steps + 1) float64, all optional."""
+        if len(targets.shape) != 2 or targets.shape[0 if flags & LGS_COORD_MAJOR else 1] != self.d:
+            raise ValueError(f"targets must be (n, {self.d}), or ({self.d}, n) with LGS_COORD_MAJOR")
+        n = targets.shape[1] if flags & LGS_COORD_MAJOR else targets.shape[0]
+        zt = "int64" if flags & LGS_Z64 else "int32"
+        outs = (logw, accepts, final_step, accepted, logw_draws, bound_draws)
+        _check_bufs(flags, self.device, ((targets, "float64", "targets"), (z_out, zt, "z_out"),
+                                         (v_out, "float64", "v_out"), (cprime_out, "float64", "cprime_out"),
+                                         (logw, "float64", "logw"), (accepts, "int64", "accepts"),
+                                         (final_step, "int64", "final_step"), (accepted, "uint8", "accepted"),
+                                         (logw_draws, "float64", "logw_draws"),
+                                         (bound_draws, "float64", "bound_draws")))
+        out = None
+        if any(a is not None for a in outs):
+            out = ImhkTargetsOutputs(*(None if a is None else _ptr(a).value for a in outs))
+        self._ck(self._L.lgs_imhk_targets(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_chain), int(n),
+                                          int(n_steps), _ptr(targets), _ptr(z_out), _ptr(v_out),
+                                          _ptr(cprime_out), None if out is None else ctypes.byref(out),
+                                          int(flags)))
+
+    def imhk_targets_host(self, seed, first_chain, targets, n_steps, *, want_z=True, want_v=True,
+                          want_cprime=False, want_trace=False, flags=0):
+        """IMHK chains around host targets (n, d) into fresh host arrays {"z", "v", "cprime",
+        "logw", "accepts", "final_step"} (and "accepted", "logw_draws", "bound_draws" with
+        want_trace); int32 coefficients first, int64 on overflow (same draws: fixed counters)."""
+        if flags & (LGS_DEVICE_PTRS | LGS_COORD_MAJOR):
+            raise ValueError("imhk_targets_host takes row-major host targets")
+        t = np.ascontiguousarray(targets, dtype=np.float64)
+        if t.ndim != 2 or t.shape[1] != self.d:
+            raise ValueError(f"targets must be (n, {self.d})")
+        T = int(n_steps)
+        if T < 0:
+            raise ValueError("n_steps must be >= 0")
+        n = t.shape[0]
+        for z64 in (bool(flags & LGS_Z64), True):
+            f = flags | (LGS_Z64 if z64 else 0)
+            z = np.empty((n, self.d), dtype=np.int64 if z64 else np.int32) if want_z else None
+            v = np.empty((n, self.d)) if want_v else None
+            cp = np.empty((n, self.d)) if want_cprime else None
+            lw, acc, fs = np.empty(n), np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
+            tr = np.empty((n, T), dtype=np.uint8) if want_trace else None
+            ld = np.empty((n, T + 1)) if want_trace else None
+            bd = np.empty((n, T + 1)) if want_trace else None
+            try:
+                self.imhk_targets(seed, first_chain, t, T, z, v, cp, lw, acc, fs, tr, ld, bd, f)
+            except LgsError as e:
+                if e.code == LGS_ERR_OVERFLOW and not z64:
+                    continue
+                raise
+            r = {"z": None if z is None else z.astype(np.int64, copy=False), "v": v, "cprime": cp,
+                 "logw": lw, "accepts": acc, "final_step": fs}
+            if want_trace:
+                r["accepted"], r["logw_draws"], r["bound_draws"] = tr, ld, bd
             return r
         raise AssertionError("unreachable")
 

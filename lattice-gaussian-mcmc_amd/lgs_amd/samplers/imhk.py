@@ -37,14 +37,16 @@ class IMHKSampler(DiscreteGaussianSampler):
     def __init__(self, lattice, sigma: float, center: Optional[np.ndarray] = None,
                  precision: int = 10, burn_in: Optional[int] = None, *,
                  seed: Optional[int] = None, device: int = 0, wang_ling: bool = False,
-                 exact_order: bool = False, chain_id: int = 0):
+                 exact_order: bool = False, chain_id: int = 0,
+                 context: Optional[_capi.Context] = None):
         super().__init__(lattice, sigma, center)
         self.seed = _default_seed() if seed is None else int(seed)
         self.proposal_sampler = RefinedKleinSampler(lattice, sigma, center, precision,
                                                     seed=self.seed, device=device,
-                                                    exact_order=exact_order)
+                                                    exact_order=exact_order, context=context)
         self.wang_ling = wang_ling
         self.chain_id = int(chain_id)
+        self._next_around_chain = self.chain_id + 1  # sample_around's chains: never the sampler's own
         self.burn_in = burn_in if burn_in is not None else self._estimate_burn_in()
         self.total_proposals = 0
         self.accepted_proposals = 0
@@ -212,6 +214,56 @@ class IMHKSampler(DiscreteGaussianSampler):
         idx = np.arange(0, num_steps, save_every)
         pts = self.context.lattice_points(zs[idx])
         return [p.copy() for p in pts]
+
+    def sample_around(self, targets, n_steps: int, coefficients: bool = False,
+                      first_chain: Optional[int] = None):
+        """One lattice point near each target, from an IMHK chain of its own: target k
+        gets the state after ``n_steps`` Metropolis steps with Wang-Ling weights over Klein
+        draws around t_k (``lgs_imhk_targets``), which removes the bias Klein's draw has
+        when sigma is below the smoothing bound (``KleinSampler.sample_around`` is the
+        chain's step 0).  A (d,) target gives a (d,) point, (n, d) targets give (n, d);
+        with coefficients=True returns (points, z).  Chains are numbered from an internal
+        counter that starts at chain_id + 1 and advances by n per call (``first_chain``
+        overrides it for this call), so they never share a counter with the sampler's own
+        chain, whose state, step counter and acceptance totals are untouched.
+        ``stats.acceptance_rate`` is set to this call's accepted fraction."""
+        t = np.asarray(targets, dtype=np.float64)
+        single = t.ndim == 1
+        if single:
+            t = t[None, :]
+        if t.ndim != 2 or t.shape[1] != self.dimension:
+            raise ValueError(f"targets must be ({self.dimension},) or (n, {self.dimension}), got {np.shape(targets)}")
+        if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or n_steps < 0:
+            raise ValueError(f"n_steps must be a non-negative integer, got {n_steps!r}")
+        if first_chain is not None and (isinstance(first_chain, bool) or
+                                        not isinstance(first_chain, (int, np.integer)) or first_chain < 0):
+            raise ValueError(f"first_chain must be a non-negative integer, got {first_chain!r}")
+        n, T = t.shape[0], int(n_steps)
+        if n == 0:
+            z0 = np.zeros((0, self.dimension), dtype=int)
+            return (np.zeros((0, self.dimension)), z0) if coefficients else np.zeros((0, self.dimension))
+        ps = self.proposal_sampler
+        if ps._uploaded_precision != ps.precision:
+            ps._upload(ps.precision)
+        if not ps._decoder_uploaded:
+            ps.context.set_decoder(Q=ps.Q)
+            ps._decoder_uploaded = True
+        start = time.time()
+        if first_chain is None:
+            first = self._next_around_chain
+            self._next_around_chain += n
+        else:
+            first = int(first_chain)
+        r = ps.context.imhk_targets_host(self.seed, first, t, T, want_z=coefficients, want_v=True,
+                                         flags=ps._flags())
+        self.stats.samples_generated += n
+        self.stats.time_elapsed += time.time() - start
+        self.stats.acceptance_rate = float(r["accepts"].sum()) / (n * T) if T > 0 else 0.0
+        v = r["v"][0] if single else r["v"]
+        if not coefficients:
+            return v
+        z = r["z"].astype(int)
+        return v, (z[0] if single else z)
 
     def estimate_spectral_gap(self, num_samples: int = 1000) -> float:
         """imhk.py:252-284: 1 / max importance weight over Klein proposals."""
