@@ -234,6 +234,17 @@ def _check_bufs(flags, device, bufs):
             raise ValueError(f"{name}: on cuda:{a.device.index}, context on cuda:{device}")
 
 
+def _check_padded(x, shape, ld):
+    """x must hold the logical `shape` (rows, cols) at row pitch ld: the library reads
+    (rows - 1) * ld + cols elements from its pointer."""
+    rows, cols = shape
+    have = 1
+    for s in x.shape:
+        have *= int(s)
+    if ld < cols or (rows > 0 and have < (rows - 1) * ld + cols):
+        raise ValueError(f"buffer of {have} elements does not hold shape {shape} at leading dimension {ld}")
+
+
 def x_flags(a) -> int:
     """LGS_X_* element-type flag of a host array / device tensor (fp64, int32, int64)."""
     t = _dtype_name(a)
@@ -625,20 +636,32 @@ class Context:
                                      _ptr(c0), _ptr(acf), _ptr(tau), _ptr(batch_means),
                                      int(flags | x_flags(x))))
 
-    def gram(self, x, shift=None, sum_out=None, gram_out=None, coord_major=False, flags=0):
+    def gram(self, x, shift=None, sum_out=None, gram_out=None, coord_major=False, flags=0, ldx=None,
+             shape=None):
         """sum y and sum y y^T, y = x - shift, ADDED to sum_out (d) / gram_out (d x d):
-        int64 (exact) for int32 / int64 x, fp64 for float64 x."""
+        int64 (exact) for int32 / int64 x, fp64 for float64 x.  ldx (default: the row
+        length of x) is the leading dimension in elements; x is then the padded 2-D
+        buffer and shape its logical shape, (d, n) coordinate-major or (n, d)."""
         f = flags | (LGS_COORD_MAJOR if coord_major else 0) | x_flags(x)
+        shape = tuple(x.shape) if shape is None else tuple(shape)
         if coord_major:
-            d, n = x.shape
+            d, n = shape
         else:
-            n, d = x.shape
-        self._ck(self._L.lgs_gram(self._h, int(d), int(n), _ptr(x), int(n if coord_major else d),
+            n, d = shape
+        if ldx is None:
+            ldx = n if coord_major else d
+        _check_padded(x, shape, int(ldx))
+        self._ck(self._L.lgs_gram(self._h, int(d), int(n), _ptr(x), int(ldx),
                              _ptr(shift), _ptr(sum_out), _ptr(gram_out), int(f)))
 
-    def jump_distance(self, x, out, flags=0):
-        n, d = x.shape
-        self._ck(self._L.lgs_jump_distance(self._h, int(n), int(d), _ptr(x), int(d), _ptr(out),
+    def jump_distance(self, x, out, flags=0, ld=None, shape=None):
+        """||x[t+1] - x[t]||_2 of the rows of x (n x d) into out (n - 1).  ld (default d)
+        is the row pitch in elements; x is then the padded buffer, shape the logical (n, d)."""
+        n, d = tuple(x.shape) if shape is None else tuple(shape)
+        if ld is None:
+            ld = d
+        _check_padded(x, (n, d), int(ld))
+        self._ck(self._L.lgs_jump_distance(self._h, int(n), int(d), _ptr(x), int(ld), _ptr(out),
                                       int(flags | x_flags(x))))
 
     def marginal_tvd(self, x1, x2, out, flags=0):
