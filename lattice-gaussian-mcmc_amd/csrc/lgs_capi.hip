@@ -204,8 +204,8 @@ struct lgs_ctx {
     int zint = 2;  // internal coefficient store width (bytes): 16-bit, sticky 32-bit on overflow; LGS_ZINT=4 forces 32-bit
     // timing
     bool timing = false;
-    double t_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int64_t t_n[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double t_ms[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t t_n[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // diagnostics scratch (lgs_series_stats / lgs_gram / lgs_jump_distance / lgs_marginal_tvd)
     DevBuf dg_x, dg_y, dg_out, dg_a, dg_b, dg_c, dg_t;
     // decoding frame (lgs_set_decoder): Q of the QR and (B^{-1})^T, row-major d x d
@@ -218,6 +218,10 @@ struct lgs_ctx {
     // final step and accepted trace (its per-draw weights and bounds: LW, LWE; its final
     // columns and compact store: DEC_WIN, DEC_Z)
     DevBuf IT_LOGW, IT_ACC, IT_STEP, IT_TRACE;
+    // lgs_closest_vector: the two search state blocks (compaction copies one into the other),
+    // the hand-out / live counters, the compaction map, the chunk's radius2 (host pointers)
+    // and its per-target distance, node count and status (its returned points: DEC_Z)
+    DevBuf CVP_ST[2], CVP_CTL, CVP_MAP, CVP_RAD, CVP_D2, CVP_NODES, CVP_STATUS;
     bool has_q = false, has_binv = false;
     std::vector<Timer> pending;
     std::vector<hipEvent_t> pool;
@@ -2164,7 +2168,7 @@ int lgs_timing_enable(lgs_ctx* c, int enable) {
         fold_timers(c);
     }
     c->timing = enable != 0;
-    for (int k = 0; k < 9; ++k) {
+    for (int k = 0; k < 10; ++k) {
         c->t_ms[k] = 0;
         c->t_n[k] = 0;
     }
@@ -2173,7 +2177,7 @@ int lgs_timing_enable(lgs_ctx* c, int enable) {
 
 int lgs_timing_get(lgs_ctx* c, int kernel, double* ms, int64_t* n) {
     if (!c) return fail(LGS_ERR_INVALID, "null context");
-    if (kernel < 0 || kernel > 8) return fail(LGS_ERR_INVALID, "kernel id 0..8");
+    if (kernel < 0 || kernel > 9) return fail(LGS_ERR_INVALID, "kernel id 0..9");
     if (!c->pending.empty()) {  // launches of an early-checked call may still be running
         int rc = check_ctx(c, false);
         if (rc) return rc;
@@ -3087,6 +3091,190 @@ int lgs_imhk_targets(lgs_ctx* c, uint64_t seed, uint64_t first_chain, int64_t n,
         if (cprime_out) {  // row-major, the centres the kernel read
             void* dst = dev ? (void*)(cprime_out + (size_t)off * d) : c->stage_b.p;
             HIP_TRY(lgs::launch::transpose_out(X, 8, ldc, m, (int)d, dst, 8, c->stream));
+            if (!dev)
+                HIP_TRY(hipMemcpyAsync(cprime_out + (size_t)off * d, dst, (size_t)m * d * 8, hipMemcpyDeviceToHost,
+                                       c->stream));
+        }
+        if (v_out) {
+            double* V = dev ? v_out + (size_t)off * d : c->V.as<double>();
+            if ((rc = run_bz(c, Wp, ob, ldw, m, V))) return rc;
+            if ((rc = settle_bz(c))) return rc;
+            if (!dev)
+                HIP_TRY(hipMemcpyAsync(v_out + (size_t)off * d, V, (size_t)m * d * 8, hipMemcpyDeviceToHost,
+                                       c->stream));
+        }
+        if ((rc = finish(c))) return rc;
+    }
+    return finish(c);
+}
+
+// Exact closest vector: Schnorr-Euchner enumeration (lgs_cvp.hip).  Per chunk of
+// max_proposals targets: the centres into CPT (timer 7); the enumeration (timer 9): S =
+// min(chunk, kCvpMaxSlots) lanes, each launch bounded by `slice` nodes per lane, a lane
+// whose target stops takes the next waiting one, and once none waits and at most half the
+// lanes still work the live slots are compacted into the other state block (timer 8), so
+// a few deep trees do not hold waves of idle lanes; the points of the m targets, written by
+// the kernel into the compact store, into the caller's layout; B z.
+int lgs_closest_vector(lgs_ctx* c, int64_t n, const double* targets, const double* radius2, int64_t max_nodes,
+                       void* z_out, double* v_out, double* cprime_out, const lgs_cvp_outputs* out,
+                       uint32_t flags) {
+    int rc = check_ctx(c);
+    if (rc) return rc;
+    if (flags & ~(uint32_t)(LGS_DEVICE_PTRS | LGS_Z64 | LGS_COORD_MAJOR | LGS_TARGETS_QFRAME))
+        return fail(LGS_ERR_INVALID, "lgs_closest_vector: unsupported flag 0x%x", flags);
+    if (c->d > LGS_CVP_MAX_D)
+        return fail(LGS_ERR_INVALID, "lgs_closest_vector: d = %lld > LGS_CVP_MAX_D (%d)", (long long)c->d,
+                    LGS_CVP_MAX_D);
+    if (max_nodes < 1 || max_nodes > ((int64_t)1 << 40))
+        return fail(LGS_ERR_INVALID, "max_nodes must be 1..2^40");
+    if (n < 0) return fail(LGS_ERR_INVALID, "n < 0");
+    if (n == 0) return LGS_OK;
+    if (!targets) return fail(LGS_ERR_INVALID, "null targets");
+    const bool dev = flags & LGS_DEVICE_PTRS, z64 = flags & LGS_Z64, cm = flags & LGS_COORD_MAJOR,
+               qframe = flags & LGS_TARGETS_QFRAME;
+    if (!qframe && (!c->has_q || c->DQ.bytes < (size_t)c->d * c->d * 8))
+        return fail(LGS_ERR_STATE, "targets in the lattice frame need Q (lgs_set_decoder)");
+    if (v_out && !c->has_B) return fail(LGS_ERR_STATE, "v_out requires B");
+    if (radius2) {  // (a device buffer is read back: the check is the host's)
+        std::vector<double> rh;
+        const double* r = radius2;
+        if (dev) {
+            rh.resize((size_t)n);
+            HIP_TRY(hipMemcpyAsync(rh.data(), radius2, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            r = rh.data();
+        }
+        for (int64_t k = 0; k < n; ++k)
+            if (!(r[k] >= 0.0)) return fail(LGS_ERR_INVALID, "radius2[%lld] is NaN or negative", (long long)k);
+    }
+    const lgs_cvp_outputs none{};
+    const lgs_cvp_outputs& o = out ? *out : none;
+    const int64_t d = c->d;
+    const int ob = z64 ? 8 : 4;
+    if ((rc = reset_flags(c))) return rc;
+    int64_t slice = lgs::kCvpSlice, slots = lgs::kCvpMaxSlots;
+    // (hooks build) LGS_TEST_CVP_SLICE / LGS_TEST_CVP_SLOTS: nodes per lane and launch, lanes
+    // per launch (rounded up to whole waves) -- tests suspend and resume every search, and
+    // make targets wait for a slot
+    if (const char* s = hook("LGS_TEST_CVP_SLICE")) slice = std::max<int64_t>(1, atoll(s));
+    if (const char* s = hook("LGS_TEST_CVP_SLOTS")) slots = std::max<int64_t>(1, atoll(s));
+    const int64_t chunk = std::min<int64_t>(n, c->max_props);
+    const int64_t ldw = (chunk + 63) / 64 * 64;
+    const int64_t S = std::min<int64_t>(ldw, (slots + 63) / 64 * 64);
+    if ((rc = c->CPT.reserve((size_t)ldw * d * 8)) || (rc = c->DEC_Z.reserve((size_t)ldw * d * ob)) ||
+        (rc = c->CVP_ST[0].reserve(lgs::cvp_state_bytes((int)d, S))) ||
+        (rc = c->CVP_ST[1].reserve(lgs::cvp_state_bytes((int)d, S))) || (rc = c->CVP_CTL.reserve(16)) ||
+        (rc = c->CVP_MAP.reserve((size_t)S * 4)) || (rc = c->CVP_D2.reserve((size_t)chunk * 8)) ||
+        (rc = c->CVP_NODES.reserve((size_t)chunk * 8)) || (rc = c->CVP_STATUS.reserve((size_t)chunk * 4)))
+        return rc;
+    if (!qframe && ((rc = c->dg_x.reserve((size_t)chunk * d * 8)) || (rc = c->dg_y.reserve((size_t)chunk * d * 8))))
+        return rc;
+    if (!dev) {
+        if ((rc = c->stage_a.reserve((size_t)chunk * d * 8))) return rc;
+        if (cprime_out && (rc = c->stage_b.reserve((size_t)chunk * d * 8))) return rc;
+        if (v_out && (rc = c->V.reserve((size_t)chunk * d * 8))) return rc;
+        if (radius2 && (rc = c->CVP_RAD.reserve((size_t)chunk * 8))) return rc;
+    }
+    const lgs::CvpState st[2] = {lgs::cvp_state_at(c->CVP_ST[0].p, (int)d, S),
+                                 lgs::cvp_state_at(c->CVP_ST[1].p, (int)d, S)};
+    double* X = c->CPT.as<double>();
+    std::vector<int32_t> tgt_h, map_h;
+    for (int64_t off = 0; off < n; off += chunk) {
+        const int64_t m = std::min<int64_t>(chunk, n - off);
+        if ((rc = stage_centres(c, targets, n, off, m, X, ldw, dev, cm, qframe))) return rc;
+        lgs::CvpArgs a{};
+        a.d = (int)d;
+        a.m = m;
+        a.S = S;
+        a.max_nodes = max_nodes;
+        a.slice = slice;
+        a.R = c->R.as<double>();
+        a.CP = X;
+        a.ldc = ldw;
+        a.radius2 = nullptr;
+        if (radius2) {
+            if (dev) {
+                a.radius2 = radius2 + off;
+            } else {
+                HIP_TRY(hipMemcpyAsync(c->CVP_RAD.p, radius2 + off, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+                a.radius2 = c->CVP_RAD.as<double>();
+            }
+        }
+        a.ctl = c->CVP_CTL.as<unsigned long long>();
+        a.W = c->DEC_Z.p;
+        a.ldw = ldw;
+        a.dist2 = dev && o.dist2 ? o.dist2 + off : c->CVP_D2.as<double>();
+        a.nodes = dev && o.nodes ? o.nodes + off : c->CVP_NODES.as<int64_t>();
+        a.status = dev && o.status ? o.status + off : c->CVP_STATUS.as<int32_t>();
+        a.flags = c->flags.as<unsigned int>();
+        // (columns m .. ldw - 1 of the compact store stay zero for B z)
+        HIP_TRY(hipMemsetAsync(a.W, 0, (size_t)ldw * d * ob, c->stream));
+        HIP_TRY(hipMemsetAsync(a.ctl, 0, 16, c->stream));
+        HIP_TRY(hipMemsetAsync(st[0].tgt, 0xff, (size_t)S * 4, c->stream));  // every slot idle
+        int cur = 0;
+        int64_t live = std::min<int64_t>(S, m);
+        // Launches: while a target waits every lane uses its whole slice, so at most
+        // m max_nodes / (live slice) launches end with one waiting; after that every search
+        // is resumed at most ceil(max_nodes / slice) times, and one launch hands out.
+        const double bound = std::ceil((double)m * (double)max_nodes / ((double)live * (double)slice)) +
+                             std::ceil((double)max_nodes / (double)slice) + 2.0;
+        for (double launches = 0.0;; launches += 1.0) {
+            if (launches > bound) return fail(LGS_ERR_HIP, "lgs_closest_vector: launch bound exceeded (a library bug)");
+            a.st = st[cur];
+            a.nslots = live;
+            HIP_TRY(hipMemsetAsync(a.ctl + 1, 0, 8, c->stream));
+            {
+                Scope s(c, 9);
+                HIP_TRY(lgs::launch::cvp_enum(a, ob, c->stream));
+            }
+            unsigned long long ctl[2] = {0, 0};
+            HIP_TRY(hipMemcpyAsync(ctl, a.ctl, 16, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            const int64_t nact = (int64_t)ctl[1];
+            if (ctl[0] < (unsigned long long)m) continue;  // targets still wait for a slot
+            if (nact == 0) break;
+            if (nact * 2 <= live && live > 64) {  // compact the unfinished searches
+                tgt_h.resize((size_t)live);
+                HIP_TRY(hipMemcpy(tgt_h.data(), st[cur].tgt, (size_t)live * 4, hipMemcpyDeviceToHost));
+                map_h.clear();
+                for (int64_t s = 0; s < live; ++s)
+                    if (tgt_h[(size_t)s] >= 0) map_h.push_back((int32_t)s);
+                if ((int64_t)map_h.size() != nact)
+                    return fail(LGS_ERR_HIP, "lgs_closest_vector: live count mismatch (a library bug)");
+                HIP_TRY(hipMemcpyAsync(c->CVP_MAP.p, map_h.data(), (size_t)nact * 4, hipMemcpyHostToDevice, c->stream));
+                {
+                    Scope s(c, 8);
+                    HIP_TRY(lgs::launch::cvp_compact(st[cur], st[cur ^ 1], S, c->CVP_MAP.as<int32_t>(), nact, (int)d,
+                                                     c->stream));
+                }
+                HIP_TRY(hipStreamSynchronize(c->stream));  // (map_h is pageable host memory)
+                cur ^= 1;
+                live = nact;
+            }
+        }
+        void* Wp = a.W;
+        c->hist.Z = nullptr;  // (no int16 history: B z reads the compact store)
+        if (z_out) {
+            if (cm) {
+                HIP_TRY(hipMemcpy2DAsync((char*)z_out + (size_t)off * ob, (size_t)n * ob, Wp, (size_t)ldw * ob,
+                                         (size_t)m * ob, (size_t)d, kind_of(dev, true), c->stream));
+            } else {
+                void* dst = dev ? (char*)z_out + (size_t)off * d * ob : c->stage_a.p;
+                HIP_TRY(lgs::launch::transpose_out(Wp, ob, ldw, m, (int)d, dst, ob, c->stream));
+                if (!dev)
+                    HIP_TRY(hipMemcpyAsync((char*)z_out + (size_t)off * d * ob, dst, (size_t)m * d * ob,
+                                           hipMemcpyDeviceToHost, c->stream));
+            }
+        }
+        if (!dev) {
+            if (o.dist2) HIP_TRY(hipMemcpyAsync(o.dist2 + off, a.dist2, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
+            if (o.nodes) HIP_TRY(hipMemcpyAsync(o.nodes + off, a.nodes, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
+            if (o.status)
+                HIP_TRY(hipMemcpyAsync(o.status + off, a.status, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+        }
+        if (cprime_out) {  // row-major, the centres the kernel read
+            void* dst = dev ? (void*)(cprime_out + (size_t)off * d) : c->stage_b.p;
+            HIP_TRY(lgs::launch::transpose_out(X, 8, ldw, m, (int)d, dst, 8, c->stream));
             if (!dev)
                 HIP_TRY(hipMemcpyAsync(cprime_out + (size_t)off * d, dst, (size_t)m * d * 8, hipMemcpyDeviceToHost,
                                        c->stream));

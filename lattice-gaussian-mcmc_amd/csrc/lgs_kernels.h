@@ -236,6 +236,69 @@ struct ImhkTargetsArgs {
     double bscale;          // bounds x bscale (1; a test hook widens them to force recomputations)
 };
 
+// ---- exact closest vector: Schnorr-Euchner enumeration (lgs_cvp.hip, lgs_closest_vector)
+constexpr int kCvpMaxD = 64;               // LGS_CVP_MAX_D: R fits 32 KB of LDS
+constexpr int64_t kCvpSlice = 1 << 16;     // tree nodes a lane visits per launch at most
+constexpr int64_t kCvpMaxSlots = 1 << 16;  // lanes of one launch (the state block's columns)
+constexpr int kCvpLanes = 64;              // lanes of a block: one wave
+constexpr double kCvpMaxAbsZ = 4503599627370496.0;  // 2^52: a conditional mean at or beyond it is an error
+// LDS of a block: R, then base | P | z | sn of its lanes (lgs_cvp.hip)
+inline size_t cvp_lds_bytes(int d) { return ((size_t)d * d + (size_t)4 * d * kCvpLanes) * 8; }
+// The search state of one slot (= lane): element (i, s) of a per-level array at
+// [i * S + s], S the slot count of the block, so the lanes of a wave that stand on the same
+// level read adjacent addresses.  It persists between launches: a launch loads the scalars,
+// advances the search by at most `slice` nodes and stores them back.
+struct CvpState {
+    double* z;       // d x S: the current point's coefficients (integers, |z| < 2^53)
+    double* base;    // d x S: c'_i - cs of the level's entry
+    double* P;       // d x S: partial distance of levels >= i (row 0 unused, P[d] = 0 implied)
+    double* sn;      // d x S: stp * (nxt + 1), the zig-zag's next offset with its sign (an integer)
+    int64_t* best;   // d x S: the best point found
+    double* A;       // S: the bound (radius2, then the best point's distance)
+    int64_t* nodes;  // S: nodes visited for the slot's target
+    int32_t* tgt;    // S: the chunk's target the slot works on, -1 = idle
+    int32_t* lvl;    // S: the level i
+    int32_t* has_best;  // S
+};
+inline size_t cvp_state_bytes(int d, int64_t S) { return (size_t)S * ((size_t)d * 40 + 28); }
+inline CvpState cvp_state_at(void* p, int d, int64_t S) {  // (S a multiple of 64: every array 8-byte aligned)
+    CvpState s;
+    const size_t n = (size_t)d * S;
+    s.z = (double*)p;
+    s.base = s.z + n;
+    s.P = s.base + n;
+    s.sn = s.P + n;
+    s.best = (int64_t*)(s.sn + n);
+    s.A = (double*)(s.best + n);
+    s.nodes = (int64_t*)(s.A + S);
+    s.tgt = (int32_t*)(s.nodes + S);
+    s.lvl = s.tgt + S;
+    s.has_best = s.lvl + S;
+    return s;
+}
+struct CvpArgs {
+    int d;
+    int64_t m;          // targets of the chunk
+    int64_t nslots;     // lanes of this launch (slots [0, nslots) of the block)
+    int64_t S;          // the state block's slot count
+    int64_t max_nodes;  // per target
+    int64_t slice;      // per lane and launch
+    const double* R;    // row-major d x d
+    const double* CP;   // the targets' centres, coordinate-major: CP[i * ldc + t]
+    int64_t ldc;
+    const double* radius2;  // nullable, m
+    CvpState st;
+    // ctl[0]: the next target to hand out (an idle lane takes it; >= m: none left);
+    // ctl[1]: slots still working on a target when the launch ended (zeroed before it)
+    unsigned long long* ctl;
+    void* W;            // the returned points, coordinate-major, ld ldw, 4- or 8-byte elements
+    int64_t ldw;
+    double* dist2;      // m
+    int64_t* nodes;     // m
+    int32_t* status;    // m
+    unsigned int* flags;  // the context's flag words (kFlagNonFinite, kFlagOverflow)
+};
+
 struct AcceptArgs {
     int64_t nc;
     int64_t T;
@@ -463,6 +526,14 @@ hipError_t decode_select(int d, int64_t m, int64_t K, const double* D, const dou
 // caller's layout), both of width zb.
 hipError_t decode_gather(int d, int64_t m, const int64_t* win, const void* Z, int zb, int64_t ldz, void* W,
                          int64_t ldw, void* out, int64_t st_t, int64_t st_i, hipStream_t st);
+// ---- exact closest vector (lgs_cvp.hip)
+// One launch of the enumeration: every slot of [0, a.nslots) advances its target's search by
+// at most a.slice nodes; an idle slot (and one whose target stops) takes the next target
+// from a.ctl[0].  zb 4 or 8: the element width of a.W.  d <= kCvpMaxD.
+hipError_t cvp_enum(const CvpArgs& a, int zb, hipStream_t st);
+// Slots map[0 .. nlive) of src into slots 0 .. nlive - 1 of dst (blocks of S slots each)
+hipError_t cvp_compact(const CvpState& src, const CvpState& dst, int64_t S, const int32_t* map, int64_t nlive,
+                       int d, hipStream_t st);
 hipError_t round_coeffs(const double* W, int64_t ldw, int d, int64_t n, int zb, void* Z, int64_t ldz,
                         unsigned int* flags, hipStream_t st);
 hipError_t check_range16(const void* zs, int ob, int64_t count, unsigned int* flags, hipStream_t st);

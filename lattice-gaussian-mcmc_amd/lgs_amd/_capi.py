@@ -54,6 +54,8 @@ KERNEL_KLEIN, KERNEL_BZ, KERNEL_ACCEPT, KERNEL_MOMENTS = 0, 1, 2, 3
 KERNEL_GRAM, KERNEL_SERIES, KERNEL_KLEIN_INIT = 4, 5, 6
 KERNEL_CPRIME = 7  # lgs_klein_targets: the c' = Q^T t stage (transposes + GEMM)
 KERNEL_DECODE_SELECT = 8  # lgs_klein_decode: the select and gather launches; lgs_imhk_targets: scan and gather
+KERNEL_CVP_ENUM = 9  # lgs_closest_vector: the enumeration launches
+LGS_CVP_MAX_D = 64
 LGS_COUNTER_RESOLVED = 0
 LGS_COUNTER_FALLBACK = 1
 LGS_COUNTER_ACCEPT_RESOLVED = 2
@@ -73,7 +75,7 @@ EXPORTS = ("lgs_version", "lgs_last_error", "lgs_create", "lgs_create_ex", "lgs_
            "lgs_timing_get", "lgs_device_info", "lgs_series_stats", "lgs_gram",
            "lgs_jump_distance", "lgs_marginal_tvd", "lgs_column_range", "lgs_histogram", "lgs_set_decoder", "lgs_nearest_plane",
            "lgs_round_decode", "lgs_counter", "lgs_qskip_elided", "lgs_klein_targets", "lgs_klein_decode",
-           "lgs_imhk_targets")
+           "lgs_imhk_targets", "lgs_closest_vector")
 
 
 class ImhkOutputs(ctypes.Structure):
@@ -95,6 +97,11 @@ class ImhkTargetsOutputs(ctypes.Structure):
     """struct lgs_imhk_targets_outputs (include/lgs.h)."""
     _fields_ = [("logw", ctypes.c_void_p), ("accepts", ctypes.c_void_p), ("final_step", ctypes.c_void_p),
                 ("accepted", ctypes.c_void_p), ("logw_draws", ctypes.c_void_p), ("bound_draws", ctypes.c_void_p)]
+
+
+class CvpOutputs(ctypes.Structure):
+    """struct lgs_cvp_outputs (include/lgs.h)."""
+    _fields_ = [("dist2", ctypes.c_void_p), ("nodes", ctypes.c_void_p), ("status", ctypes.c_void_p)]
 
 
 class LgsError(RuntimeError):
@@ -179,6 +186,9 @@ def load_library(path: str = LIB_PATH):
     if hasattr(L, "lgs_imhk_targets"):  # (older A/B baselines lack it)
         L.lgs_imhk_targets.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, _i64, _i64, _vp, _vp, _vp, _vp,
                                        ctypes.POINTER(ImhkTargetsOutputs), ctypes.c_uint32]
+    if hasattr(L, "lgs_closest_vector"):  # (older A/B baselines lack it)
+        L.lgs_closest_vector.argtypes = [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, ctypes.POINTER(CvpOutputs),
+                                         ctypes.c_uint32]
     for name in EXPORTS:
         if name not in ("lgs_version", "lgs_last_error") and hasattr(L, name):
             getattr(L, name).restype = ctypes.c_int
@@ -622,6 +632,79 @@ class Context:
             if want_trace:
                 r["accepted"], r["logw_draws"], r["bound_draws"] = tr, ld, bd
             return r
+        raise AssertionError("unreachable")
+
+    # ---------------------------------------------------------------- exact closest vector
+    _CVP_FLAGS = LGS_DEVICE_PTRS | LGS_Z64 | LGS_COORD_MAJOR | LGS_TARGETS_QFRAME
+
+    def _cvp_args(self, targets, max_nodes, flags):
+        """Argument checks of closest_vector / closest_vector_host, before any library call."""
+        if isinstance(flags, bool) or not isinstance(flags, (int, np.integer)) or flags & ~self._CVP_FLAGS:
+            raise ValueError(f"closest_vector: unsupported flags {flags!r}")
+        if self.d > LGS_CVP_MAX_D:
+            raise ValueError(f"closest_vector supports d <= {LGS_CVP_MAX_D}, the loaded basis has d = {self.d}")
+        if isinstance(max_nodes, bool) or not isinstance(max_nodes, (int, np.integer)) or \
+                not 1 <= max_nodes <= 1 << 40:
+            raise ValueError(f"max_nodes must be an integer in 1..2^40, got {max_nodes!r}")
+        cm = bool(flags & LGS_COORD_MAJOR)
+        if len(targets.shape) != 2 or targets.shape[0 if cm else 1] != self.d:
+            raise ValueError(f"targets must be (n, {self.d}), or ({self.d}, n) with LGS_COORD_MAJOR")
+        return int(targets.shape[1] if cm else targets.shape[0])
+
+    def closest_vector(self, targets, max_nodes, radius2=None, z_out=None, v_out=None, cprime_out=None,
+                       dist2=None, nodes=None, status=None, flags=0):
+        """Raw lgs_closest_vector on caller buffers (numpy host or device tensors): the
+        closest lattice point of each target by Schnorr-Euchner enumeration, at most
+        max_nodes tree nodes per target.  targets as in klein_targets; radius2 (n,) float64
+        (only points with squared distance below it), dist2 (n,) float64, nodes (n,) int64,
+        status (n,) int32, all optional."""
+        n = self._cvp_args(targets, max_nodes, flags)
+        cm = bool(flags & LGS_COORD_MAJOR)
+        zt = "int64" if flags & LGS_Z64 else "int32"
+        _check_bufs(flags, self.device, ((targets, "float64", "targets"), (radius2, "float64", "radius2"),
+                                         (z_out, zt, "z_out"), (v_out, "float64", "v_out"),
+                                         (cprime_out, "float64", "cprime_out"), (dist2, "float64", "dist2"),
+                                         (nodes, "int64", "nodes"), (status, "int32", "status")))
+        for a, want, name in ((z_out, (self.d, n) if cm else (n, self.d), "z_out"), (v_out, (n, self.d), "v_out"),
+                              (cprime_out, (n, self.d), "cprime_out"), (radius2, (n,), "radius2"),
+                              (dist2, (n,), "dist2"), (nodes, (n,), "nodes"), (status, (n,), "status")):
+            if a is not None and not isinstance(a, int) and tuple(a.shape) != want:
+                raise ValueError(f"{name}: expected shape {want}, got {tuple(a.shape)}")
+        out = None
+        if not (dist2 is None and nodes is None and status is None):
+            out = CvpOutputs(*(None if a is None else _ptr(a).value for a in (dist2, nodes, status)))
+        self._ck(self._L.lgs_closest_vector(self._h, n, _ptr(targets), _ptr(radius2), int(max_nodes), _ptr(z_out),
+                                            _ptr(v_out), _ptr(cprime_out),
+                                            None if out is None else ctypes.byref(out), int(flags)))
+
+    def closest_vector_host(self, targets, max_nodes, radius2=None, *, want_z=True, want_v=True,
+                            want_cprime=False, flags=0):
+        """Exact closest vectors of host targets (n, d) into fresh host arrays {"z", "v",
+        "cprime", "dist2", "nodes", "status"}; int32 coefficients first, int64 on overflow
+        (the same search: it does not depend on the output width)."""
+        if isinstance(flags, (int, np.integer)) and flags & (LGS_DEVICE_PTRS | LGS_COORD_MAJOR):
+            raise ValueError("closest_vector_host takes row-major host targets")
+        t = np.ascontiguousarray(targets, dtype=np.float64)
+        n = self._cvp_args(t, max_nodes, flags)
+        r2 = None
+        if radius2 is not None:
+            r2 = np.ascontiguousarray(radius2, dtype=np.float64)
+            if r2.shape != (n,) or not np.all(r2 >= 0):
+                raise ValueError(f"radius2 must hold {n} non-negative values")
+        for z64 in (bool(flags & LGS_Z64), True):
+            f = flags | (LGS_Z64 if z64 else 0)
+            z = np.empty((n, self.d), dtype=np.int64 if z64 else np.int32) if want_z else None
+            v = np.empty((n, self.d)) if want_v else None
+            cp = np.empty((n, self.d)) if want_cprime else None
+            d2, nd, st = np.empty(n), np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int32)
+            try:
+                self.closest_vector(t, max_nodes, r2, z, v, cp, d2, nd, st, f)
+            except LgsError as e:
+                if e.code == LGS_ERR_OVERFLOW and not z64:
+                    continue
+                raise
+            return {"z": None if z is None else z.astype(np.int64, copy=False), "v": v, "cprime": cp,
+                    "dist2": d2, "nodes": nd, "status": st}
         raise AssertionError("unreachable")
 
     # ---------------------------------------------------------------- diagnostics
