@@ -902,6 +902,191 @@ hipMemcpyKind kind_of(bool dev_dst, bool dev_src) {
     return hipMemcpyHostToHost;
 }
 
+// (hooks build) LGS_TEST_Z1CAP_SCALE = s < 1 (the knob of the 32-row-panel kernels' cap):
+// the per-target sampling kernels widen every certificate bound, and every distance or
+// weight bound with it, by 1 / s, so decisions go through the reference-order path
+double test_dmu_scale() {
+    if (const char* s = hook("LGS_TEST_Z1CAP_SCALE")) {
+        const double v = atof(s);
+        if (v > 0.0 && v < 1.0) return 1.0 / v;
+    }
+    return 1.0;
+}
+
+// the flags of the per-target samplers (lgs_closest_vector: all but LGS_EXACT_ORDER)
+constexpr uint32_t kSamplerFlags = LGS_DEVICE_PTRS | LGS_Z64 | LGS_COORD_MAJOR | LGS_EXACT_ORDER | LGS_TARGETS_QFRAME;
+
+// The call frame of the entry points that take a batch of targets and give z / B z / c' of
+// each: run_decode, lgs_klein_targets, lgs_klein_decode, lgs_imhk_targets and
+// lgs_closest_vector (lgs_klein and lgs_lattice_points use its z / v tails).  An entry
+// point opens it (context, flag mask), makes its own argument checks where the order of
+// the errors has them (after "n < 0", before an empty call returns), then inputs(); it
+// chooses its chunk geometry and begin()s; per chunk it calls chunk_at(), centres(), its
+// own kernels, the tails of the outputs, and finish(c).
+struct TargetCall {
+    lgs_ctx* c;
+    int64_t n;              // targets of the call
+    const double* targets;  // (n, d), or (d, n) coordinate-major
+    void* z_out;
+    double *v_out, *cprime_out;
+    bool dev = false, z64 = false, cm = false, exact = false, qframe = false;
+    int ob = 4;             // the caller's coefficient width
+    int64_t d = 0;
+    int64_t off = 0, m = 0;  // the chunk: targets off .. off + m - 1
+
+    void set_flags(uint32_t flags) {
+        dev = flags & LGS_DEVICE_PTRS, z64 = flags & LGS_Z64, cm = flags & LGS_COORD_MAJOR;
+        exact = flags & LGS_EXACT_ORDER, qframe = flags & LGS_TARGETS_QFRAME;
+        ob = z64 ? 8 : 4;
+        d = c->d;
+    }
+
+    int open(const char* fn, uint32_t flags, uint32_t allowed) {
+        const int rc = check_ctx(c);
+        if (rc) return rc;
+        if (flags & ~allowed) return fail(LGS_ERR_INVALID, "%s: unsupported flag 0x%x", fn, flags);
+        set_flags(flags);
+        return LGS_OK;
+    }
+
+    // what a call with n > 0 needs of its arguments and of the context
+    int inputs() {
+        if (!targets) return fail(LGS_ERR_INVALID, "null targets");
+        if (!qframe && (!c->has_q || c->DQ.bytes < (size_t)d * d * 8))
+            return fail(LGS_ERR_STATE, "targets in the lattice frame need Q (lgs_set_decoder)");
+        if (v_out && !c->has_B) return fail(LGS_ERR_STATE, "v_out requires B");
+        return LGS_OK;
+    }
+
+    // The first work of a call: clears the kernel flags and reserves the scratch of the
+    // stages and tails below, for chunks of at most `chunk` targets and a centre store CPT of
+    // ldc >= chunk columns (ldc = 0: none, run_decode stages into dg_x).
+    int begin(int64_t chunk, int64_t ldc) {
+        const size_t rows = (size_t)chunk * d * 8;
+        int rc = reset_flags(c);
+        if (rc) return rc;
+        if (ldc && (rc = c->CPT.reserve((size_t)ldc * d * 8))) return rc;
+        if (!qframe && ((rc = c->dg_x.reserve(rows)) || (rc = c->dg_y.reserve(rows)))) return rc;
+        if (dev) return LGS_OK;
+        if ((rc = c->stage_a.reserve(rows))) return rc;
+        if (cprime_out && (rc = c->stage_b.reserve(rows))) return rc;
+        if (v_out && (rc = c->V.reserve(rows))) return rc;
+        return LGS_OK;
+    }
+
+    int64_t chunk_at(int64_t o, int64_t chunk) {
+        off = o;
+        return m = std::min<int64_t>(chunk, n - o);
+    }
+
+    // The chunk's targets, multiplied by the frame matrix MT (gemm_f64's layout; nullptr:
+    // as they are), coordinate-major into X (ld >= m columns, those from m on zeroed).
+    // Scratch: stage_a (host targets), dg_x / dg_y (with MT).
+    int stage(const double* MT, double* X, int64_t ld) {
+        if (ld > m) HIP_TRY(hipMemset2DAsync(X + m, (size_t)ld * 8, 0, (size_t)(ld - m) * 8, (size_t)d, c->stream));
+        if (!MT && cm) {
+            HIP_TRY(hipMemcpy2DAsync(X, (size_t)ld * 8, targets + off, (size_t)n * 8, (size_t)m * 8, (size_t)d,
+                                     kind_of(true, dev), c->stream));
+            return LGS_OK;
+        }
+        const double* src;  // row-major m x d on the device
+        if (cm) {           // T (d x m) for the GEMM
+            HIP_TRY(hipMemcpy2DAsync(c->dg_x.p, (size_t)m * 8, targets + off, (size_t)n * 8, (size_t)m * 8, (size_t)d,
+                                     kind_of(true, dev), c->stream));
+            src = nullptr;
+        } else {
+            src = targets + (size_t)off * d;
+            if (!dev) {
+                HIP_TRY(hipMemcpyAsync(c->stage_a.p, src, (size_t)m * d * 8, hipMemcpyHostToDevice, c->stream));
+                src = c->stage_a.as<double>();
+            }
+            if (MT) HIP_TRY(lgs::launch::to_coord_major(src, 8, m, (int)d, c->dg_x.p, 8, m, c->stream));
+        }
+        if (MT) {
+            HIP_TRY(lgs::launch::gemm_f64(c->dg_x.as<double>(), m, MT, (int)d, m, c->dg_y.as<double>(), c->stream));
+            src = c->dg_y.as<double>();
+        }
+        HIP_TRY(lgs::launch::to_coord_major(src, 8, m, (int)d, X, 8, ld, c->stream));
+        return LGS_OK;
+    }
+
+    // The c' stage of the per-target samplers (timer 7): c' = Q^T t on fp64 MFMA, or the
+    // caller's c' itself with qframe.
+    int centres(double* X, int64_t ld) {
+        Scope s(c, 7);
+        return stage(qframe ? nullptr : c->DQ.as<double>(), X, ld);
+    }
+
+    // The context's coefficient store, about to be written by another kernel than the Klein
+    // launch that keeps its q-panel key.
+    void* take_store() {
+        lgs::qkey_drop(c->qkey);
+        return c->Z.p;
+    }
+
+    // Where a kernel writes the chunk's row-major z for the caller: the caller's device
+    // buffer, or stage_a (nullptr: no z_out, or coordinate-major).
+    void* z_rows() const {
+        if (!z_out || cm) return nullptr;
+        return dev ? (char*)z_out + (size_t)off * d * ob : c->stage_a.p;
+    }
+
+    // z of the chunk out of the coordinate-major store Z (elements of zb bytes, ldz columns)
+    // into the caller's layout.  Row-major goes through transpose_out to z_rows(), unless
+    // `gathered`: decode_gather wrote the rows there already.
+    int z_tail(const void* Z, int zb, int64_t ldz, bool gathered = false) {
+        if (!z_out) return LGS_OK;
+        if (cm) {  // (zb == ob)
+            HIP_TRY(hipMemcpy2DAsync((char*)z_out + (size_t)off * ob, (size_t)n * ob, Z, (size_t)ldz * ob,
+                                     (size_t)m * ob, (size_t)d, kind_of(dev, true), c->stream));
+            return LGS_OK;
+        }
+        void* rows = z_rows();
+        if (!gathered) HIP_TRY(lgs::launch::transpose_out(Z, zb, ldz, m, (int)d, rows, ob, c->stream));
+        if (!dev)
+            HIP_TRY(hipMemcpyAsync((char*)z_out + (size_t)off * d * ob, rows, (size_t)m * d * ob, hipMemcpyDeviceToHost,
+                                   c->stream));
+        return LGS_OK;
+    }
+
+    // c' of the chunk, row-major: the centres the kernel read in X (ldc columns)
+    int cprime_tail(const double* X, int64_t ldc) {
+        if (!cprime_out) return LGS_OK;
+        void* dst = dev ? (void*)(cprime_out + (size_t)off * d) : c->stage_b.p;
+        HIP_TRY(lgs::launch::transpose_out(X, 8, ldc, m, (int)d, dst, 8, c->stream));
+        if (!dev)
+            HIP_TRY(hipMemcpyAsync(cprime_out + (size_t)off * d, dst, (size_t)m * d * 8, hipMemcpyDeviceToHost,
+                                   c->stream));
+        return LGS_OK;
+    }
+
+    // v = B z of the chunk's first m columns of the store Z (after_klein: as run_bz)
+    int v_tail(const void* Z, int zb, int64_t ldz, bool after_klein = false) {
+        if (!v_out) return LGS_OK;
+        double* V = dev ? v_out + (size_t)off * d : c->V.as<double>();
+        int rc;
+        if ((rc = run_bz(c, Z, zb, ldz, m, V, 0, 0, 0, nullptr, after_klein))) return rc;
+        if ((rc = settle_bz(c))) return rc;
+        if (!dev) HIP_TRY(hipMemcpyAsync(v_out + (size_t)off * d, V, (size_t)m * d * 8, hipMemcpyDeviceToHost, c->stream));
+        return LGS_OK;
+    }
+
+    // A per-target output array of `per` elements per target.  out_ptr: where the chunk's
+    // kernels write it -- the caller's device array at the chunk, else `scratch` (reserved by
+    // the caller).  out_copy: the chunk of it from p into the caller's array, unless the
+    // kernels wrote it there (or p is null: not computed).
+    template <typename T>
+    T* out_ptr(T* user, const DevBuf& scratch, int64_t per = 1) const {
+        return dev && user ? user + (size_t)off * per : scratch.as<T>();
+    }
+    template <typename T>
+    int out_copy(T* user, const T* p, int64_t per = 1) {
+        if (!user || !p || p == user + (size_t)off * per) return LGS_OK;
+        HIP_TRY(hipMemcpyAsync(user + (size_t)off * per, p, (size_t)m * per * sizeof(T), kind_of(dev, true), c->stream));
+        return LGS_OK;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -1438,8 +1623,10 @@ int lgs_klein(lgs_ctx* c, uint64_t seed, uint64_t first, int64_t n, void* z_out,
         if (z_out && (rc = c->stage_a.reserve((size_t)chunk * d * ob))) return rc;
         if (v_out && (rc = c->V.reserve((size_t)chunk * d * 8))) return rc;
     }
+    TargetCall t{c, n, nullptr, z_out, v_out, nullptr};  // (for the z / v tails)
+    t.set_flags(flags);
     for (int64_t off = 0; off < n; off += chunk) {
-        const int64_t m = std::min<int64_t>(chunk, n - off);
+        const int64_t m = t.chunk_at(off, chunk);
         lgs::KleinArgs a = base_args(c, seed);
         a.counter_mode = 0;
         a.base = first + (uint64_t)off;
@@ -1463,28 +1650,8 @@ int lgs_klein(lgs_ctx* c, uint64_t seed, uint64_t first, int64_t n, void* z_out,
             }
         }
         if ((rc = run_klein_store(c, a, exact, wl, zb, Zp, false))) return rc;
-        if (z_out && !direct) {
-            if (cm) {  // coordinate-major output through host pointers (zb == ob)
-                for (int64_t i = 0; i < d; ++i)
-                    HIP_TRY(hipMemcpy2DAsync((char*)z_out + ((size_t)i * n + off) * ob, 0,
-                                             (char*)Zp + (size_t)i * m * ob, 0, m * ob, 1,
-                                             kind_of(dev, true), c->stream));
-            } else {
-                void* dst = dev ? (char*)z_out + (size_t)off * d * ob : c->stage_a.p;
-                HIP_TRY(lgs::launch::transpose_out(Zp, zb, a.ldz, m, (int)d, dst, ob, c->stream));
-                if (!dev)
-                    HIP_TRY(hipMemcpyAsync((char*)z_out + (size_t)off * d * ob, dst, (size_t)m * d * ob,
-                                           hipMemcpyDeviceToHost, c->stream));
-            }
-        }
-        if (v_out) {
-            double* V = dev ? v_out + (size_t)off * d : c->V.as<double>();
-            if ((rc = run_bz(c, Zp, zb, a.ldz, m, V, 0, 0, 0, nullptr, true))) return rc;
-            if ((rc = settle_bz(c))) return rc;
-            if (!dev)
-                HIP_TRY(hipMemcpyAsync(v_out + (size_t)off * d, V, (size_t)m * d * 8,
-                                       hipMemcpyDeviceToHost, c->stream));
-        }
+        if (!direct && (rc = t.z_tail(Zp, zb, a.ldz))) return rc;
+        if ((rc = t.v_tail(Zp, zb, a.ldz, true))) return rc;
         if (logw_out && !dev)
             HIP_TRY(hipMemcpyAsync(logw_out + off, a.LW, (size_t)m * 8, hipMemcpyDeviceToHost,
                                    c->stream));
@@ -1524,14 +1691,11 @@ int lgs_lattice_points(lgs_ctx* c, int64_t n, const void* z, double* v_out, uint
             Zc = c->Z.p;
         }
     }
-    double* V = v_out;
-    if (!dev) {
-        if ((rc = c->V.reserve((size_t)n * d * 8))) return rc;
-        V = c->V.as<double>();
-    }
-    if ((rc = run_bz(c, Zc, zb, n, n, V))) return rc;
-    if ((rc = settle_bz(c))) return rc;
-    if (!dev) HIP_TRY(hipMemcpyAsync(v_out, V, (size_t)n * d * 8, hipMemcpyDeviceToHost, c->stream));
+    if (!dev && (rc = c->V.reserve((size_t)n * d * 8))) return rc;
+    TargetCall t{c, n, nullptr, nullptr, v_out, nullptr};  // (for the v tail)
+    t.set_flags(flags);
+    t.chunk_at(0, n);
+    if ((rc = t.v_tail(Zc, zb, n))) return rc;
     return finish(c);
 }
 
@@ -2584,43 +2748,20 @@ int run_decode(lgs_ctx* c, bool plane, int64_t n, const double* targets, void* z
         return fail(LGS_ERR_STATE, plane ? "nearest plane needs Q (lgs_set_decoder)"
                                          : "rounding decode needs B^-1 (lgs_set_decoder)");
     if (v_out && !c->has_B) return fail(LGS_ERR_STATE, "v_out requires B");
-    const bool dev = flags & LGS_DEVICE_PTRS, z64 = flags & LGS_Z64, cm = flags & LGS_COORD_MAJOR;
+    TargetCall t{c, n, targets, z_out, v_out, nullptr};
+    t.set_flags(flags & (LGS_DEVICE_PTRS | LGS_Z64 | LGS_COORD_MAJOR));
     const int64_t d = c->d;
-    const int ob = z64 ? 8 : 4;
-    if ((rc = reset_flags(c))) return rc;
+    const int ob = t.ob;
     int64_t chunk = std::min<int64_t>(n, std::max<int64_t>(256, ((int64_t)1 << 27) / d));
     // (hooks build) LGS_TEST_DECODE_CHUNK=m: chunks of m targets, so that tests reach the
     // second chunk's offsets at small n (read per call: tests set and clear it)
     if (const char* s = hook("LGS_TEST_DECODE_CHUNK")) chunk = std::min<int64_t>(n, std::max<int64_t>(1, atoll(s)));
-    if ((rc = c->dg_x.reserve((size_t)chunk * d * 8)) || (rc = c->dg_y.reserve((size_t)chunk * d * 8)) ||
-        (rc = c->Z.reserve((size_t)chunk * d * ob)))
-        return rc;
-    if (!dev) {
-        if ((rc = c->stage_a.reserve((size_t)chunk * d * std::max(ob, 8)))) return rc;
-        if (v_out && (rc = c->V.reserve((size_t)chunk * d * 8))) return rc;
-    }
-    double* X = c->dg_x.as<double>();   // targets, coordinate-major (d x m)
-    double* Y = c->dg_y.as<double>();   // M t, row-major (m x d), then coordinate-major in X
+    if ((rc = t.begin(chunk, 0)) || (rc = c->Z.reserve((size_t)chunk * d * ob))) return rc;
+    double* X = c->dg_x.as<double>();  // M t, coordinate-major (d x m)
     for (int64_t off = 0; off < n; off += chunk) {
-        const int64_t m = std::min<int64_t>(chunk, n - off);
-        // targets -> X (d x m)
-        if (cm) {
-            for (int64_t i = 0; i < d; ++i)
-                HIP_TRY(hipMemcpyAsync(X + (size_t)i * m, targets + (size_t)i * n + off, (size_t)m * 8,
-                                       kind_of(true, dev), c->stream));
-        } else {
-            const double* src = targets + (size_t)off * d;
-            if (!dev) {
-                HIP_TRY(hipMemcpyAsync(c->stage_a.p, src, (size_t)m * d * 8, hipMemcpyHostToDevice, c->stream));
-                src = c->stage_a.as<double>();
-            }
-            HIP_TRY(lgs::launch::to_coord_major(src, 8, m, (int)d, X, 8, m, c->stream));
-        }
-        HIP_TRY(lgs::launch::gemm_f64(X, m, plane ? c->DQ.as<double>() : c->DBIT.as<double>(), (int)d, m, Y,
-                                      c->stream));
-        HIP_TRY(lgs::launch::to_coord_major(Y, 8, m, (int)d, X, 8, m, c->stream));
-        void* Zp = c->Z.p;
-        lgs::qkey_drop(c->qkey);  // (written below by another kernel than the Klein launch that keeps it)
+        const int64_t m = t.chunk_at(off, chunk);
+        if ((rc = t.stage(plane ? c->DQ.as<double>() : c->DBIT.as<double>(), X, m))) return rc;
+        void* Zp = t.take_store();
         if (plane) {
             const double* co = c->coord.as<double>();
             HIP_TRY(lgs::launch::nearest_plane((int)d, m, c->panel, c->RP.as<double>(), c->RC.as<double>(),
@@ -2630,27 +2771,7 @@ int run_decode(lgs_ctx* c, bool plane, int64_t n, const double* targets, void* z
             HIP_TRY(lgs::launch::round_coeffs(X, m, (int)d, m, ob, Zp, m, c->flags.as<unsigned int>(),
                                               c->stream));
         }
-        if (z_out) {
-            if (cm) {
-                for (int64_t i = 0; i < d; ++i)
-                    HIP_TRY(hipMemcpyAsync((char*)z_out + ((size_t)i * n + off) * ob, (char*)Zp + (size_t)i * m * ob,
-                                           (size_t)m * ob, kind_of(dev, true), c->stream));
-            } else {
-                void* dst = dev ? (char*)z_out + (size_t)off * d * ob : c->stage_a.p;
-                HIP_TRY(lgs::launch::transpose_out(Zp, ob, m, m, (int)d, dst, ob, c->stream));
-                if (!dev)
-                    HIP_TRY(hipMemcpyAsync((char*)z_out + (size_t)off * d * ob, dst, (size_t)m * d * ob,
-                                           hipMemcpyDeviceToHost, c->stream));
-            }
-        }
-        if (v_out) {
-            double* V = dev ? v_out + (size_t)off * d : c->V.as<double>();
-            if ((rc = run_bz(c, Zp, ob, m, m, V))) return rc;
-            if ((rc = settle_bz(c))) return rc;
-            if (!dev)
-                HIP_TRY(hipMemcpyAsync(v_out + (size_t)off * d, V, (size_t)m * d * 8, hipMemcpyDeviceToHost,
-                                       c->stream));
-        }
+        if ((rc = t.z_tail(Zp, ob, m)) || (rc = t.v_tail(Zp, ob, m))) return rc;
         if ((rc = finish(c))) return rc;
     }
     return finish(c);
@@ -2693,50 +2814,6 @@ int lgs_round_decode(lgs_ctx* c, int64_t n, const double* targets, void* z_out, 
     return run_decode(c, false, n, targets, z_out, v_out, flags);
 }
 
-}  // extern "C"
-
-namespace {
-
-// The c' stage of the per-target samplers (timer 7): the centres of targets off .. off + m - 1
-// of the call's n, coordinate-major into X (ld >= m columns, those from m on zeroed) --
-// c' = Q^T t on fp64 MFMA, or the caller's c' itself with qframe.  Scratch: stage_a (host
-// targets), dg_x / dg_y (lattice frame), reserved by the caller for its chunk.
-int stage_centres(lgs_ctx* c, const double* targets, int64_t n, int64_t off, int64_t m, double* X, int64_t ld,
-                  bool dev, bool cm, bool qframe) {
-    const int64_t d = c->d;
-    Scope s(c, 7);
-    if (ld > m) HIP_TRY(hipMemset2DAsync(X + m, (size_t)ld * 8, 0, (size_t)(ld - m) * 8, (size_t)d, c->stream));
-    if (qframe && cm) {
-        HIP_TRY(hipMemcpy2DAsync(X, (size_t)ld * 8, targets + off, (size_t)n * 8, (size_t)m * 8, (size_t)d,
-                                 kind_of(true, dev), c->stream));
-        return LGS_OK;
-    }
-    const double* src;  // row-major m x d on the device
-    if (cm) {           // lattice frame, coordinate-major: T (d x m) for the GEMM
-        HIP_TRY(hipMemcpy2DAsync(c->dg_x.p, (size_t)m * 8, targets + off, (size_t)n * 8, (size_t)m * 8, (size_t)d,
-                                 kind_of(true, dev), c->stream));
-        src = nullptr;
-    } else {
-        src = targets + (size_t)off * d;
-        if (!dev) {
-            HIP_TRY(hipMemcpyAsync(c->stage_a.p, src, (size_t)m * d * 8, hipMemcpyHostToDevice, c->stream));
-            src = c->stage_a.as<double>();
-        }
-        if (!qframe) HIP_TRY(lgs::launch::to_coord_major(src, 8, m, (int)d, c->dg_x.p, 8, m, c->stream));
-    }
-    if (!qframe) {
-        HIP_TRY(lgs::launch::gemm_f64(c->dg_x.as<double>(), m, c->DQ.as<double>(), (int)d, m, c->dg_y.as<double>(),
-                                      c->stream));
-        src = c->dg_y.as<double>();
-    }
-    HIP_TRY(lgs::launch::to_coord_major(src, 8, m, (int)d, X, 8, ld, c->stream));
-    return LGS_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 // Klein draws around one centre per sample.  Per chunk of max_proposals targets: the
 // centres c' = Q^T t (or the caller's c') coordinate-major in CPT, padded with zeros to
 // whole waves (m -> mp lanes, timer 7); the draw into a coefficient store of the output
@@ -2745,83 +2822,36 @@ extern "C" {
 // the outputs never read.
 int lgs_klein_targets(lgs_ctx* c, uint64_t seed, uint64_t first, int64_t n, const double* targets,
                       void* z_out, double* v_out, double* cprime_out, uint32_t flags) {
-    int rc = check_ctx(c);
+    TargetCall t{c, n, targets, z_out, v_out, cprime_out};
+    int rc = t.open("lgs_klein_targets", flags, kSamplerFlags);
     if (rc) return rc;
-    if (flags & ~(uint32_t)(LGS_DEVICE_PTRS | LGS_Z64 | LGS_COORD_MAJOR | LGS_EXACT_ORDER | LGS_TARGETS_QFRAME))
-        return fail(LGS_ERR_INVALID, "lgs_klein_targets: unsupported flag 0x%x", flags);
     if (n < 0) return fail(LGS_ERR_INVALID, "n < 0");
     if (n == 0) return LGS_OK;
-    if (!targets) return fail(LGS_ERR_INVALID, "null targets");
-    const bool dev = flags & LGS_DEVICE_PTRS, z64 = flags & LGS_Z64, cm = flags & LGS_COORD_MAJOR,
-               exact = flags & LGS_EXACT_ORDER, qframe = flags & LGS_TARGETS_QFRAME;
-    if (!qframe && (!c->has_q || c->DQ.bytes < (size_t)c->d * c->d * 8))
-        return fail(LGS_ERR_STATE, "targets in the lattice frame need Q (lgs_set_decoder)");
-    if (v_out && !c->has_B) return fail(LGS_ERR_STATE, "v_out requires B");
-    const int64_t d = c->d;
-    const int ob = z64 ? 8 : 4;
-    if ((rc = reset_flags(c))) return rc;
+    if ((rc = t.inputs())) return rc;
+    const int64_t d = t.d;
+    const int ob = t.ob;
     const int64_t chunk = std::min<int64_t>(n, c->max_props);
     const int64_t chunk_p = (chunk + 63) / 64 * 64;
-    if ((rc = c->CPT.reserve((size_t)chunk_p * d * 8)) || (rc = c->Z.reserve((size_t)chunk_p * d * ob))) return rc;
-    if (!qframe && ((rc = c->dg_x.reserve((size_t)chunk * d * 8)) || (rc = c->dg_y.reserve((size_t)chunk * d * 8))))
-        return rc;
-    if (!dev) {
-        if ((rc = c->stage_a.reserve((size_t)chunk * d * 8))) return rc;
-        if (cprime_out && (rc = c->stage_b.reserve((size_t)chunk * d * 8))) return rc;
-        if (v_out && (rc = c->V.reserve((size_t)chunk * d * 8))) return rc;
-    }
-    double dmu_scale = 1.0;
-    // test hook (the knob of the 32-row-panel kernels' cap): a scale s < 1 widens every
-    // certificate bound by 1 / s, so decisions go through the reference-order path
-    if (const char* s = hook("LGS_TEST_Z1CAP_SCALE")) {
-        const double v = atof(s);
-        if (v > 0.0 && v < 1.0) dmu_scale = 1.0 / v;
-    }
+    if ((rc = t.begin(chunk, chunk_p)) || (rc = c->Z.reserve((size_t)chunk_p * d * ob))) return rc;
+    const double dmu_scale = test_dmu_scale();
     double* X = c->CPT.as<double>();
     for (int64_t off = 0; off < n; off += chunk) {
-        const int64_t m = std::min<int64_t>(chunk, n - off);
+        const int64_t m = t.chunk_at(off, chunk);
         const int64_t mp = (m + 63) / 64 * 64;
-        if ((rc = stage_centres(c, targets, n, off, m, X, mp, dev, cm, qframe))) return rc;
+        if ((rc = t.centres(X, mp))) return rc;
         lgs::KleinArgs a = base_args(c, seed);
         a.counter_mode = 0;
         a.base = first + (uint64_t)off;
         a.n = mp;
         a.ldz = mp;
-        void* Zp = c->Z.p;
-        lgs::qkey_drop(c->qkey);  // (written below by another kernel than the Klein launch that keeps it)
+        void* Zp = t.take_store();
         {
             Scope s(c, 0);
             c->hist.Z = nullptr;  // (no int16 history: B z reads the store)
             HIP_TRY(lgs::launch::klein_targets(a, c->R.as<double>(), c->RP.as<double>(), c->RC.as<double>(), c->panel,
-                                               exact, X, mp, dmu_scale, ob, Zp, c->stream));
+                                               t.exact, X, mp, dmu_scale, ob, Zp, c->stream));
         }
-        if (z_out) {
-            if (cm) {
-                HIP_TRY(hipMemcpy2DAsync((char*)z_out + (size_t)off * ob, (size_t)n * ob, Zp, (size_t)mp * ob,
-                                         (size_t)m * ob, (size_t)d, kind_of(dev, true), c->stream));
-            } else {
-                void* dst = dev ? (char*)z_out + (size_t)off * d * ob : c->stage_a.p;
-                HIP_TRY(lgs::launch::transpose_out(Zp, ob, mp, m, (int)d, dst, ob, c->stream));
-                if (!dev)
-                    HIP_TRY(hipMemcpyAsync((char*)z_out + (size_t)off * d * ob, dst, (size_t)m * d * ob,
-                                           hipMemcpyDeviceToHost, c->stream));
-            }
-        }
-        if (cprime_out) {  // row-major, the centres the kernel read
-            void* dst = dev ? (void*)(cprime_out + (size_t)off * d) : c->stage_b.p;
-            HIP_TRY(lgs::launch::transpose_out(X, 8, mp, m, (int)d, dst, 8, c->stream));
-            if (!dev)
-                HIP_TRY(hipMemcpyAsync(cprime_out + (size_t)off * d, dst, (size_t)m * d * 8, hipMemcpyDeviceToHost,
-                                       c->stream));
-        }
-        if (v_out) {
-            double* V = dev ? v_out + (size_t)off * d : c->V.as<double>();
-            if ((rc = run_bz(c, Zp, ob, mp, m, V))) return rc;
-            if ((rc = settle_bz(c))) return rc;
-            if (!dev)
-                HIP_TRY(hipMemcpyAsync(v_out + (size_t)off * d, V, (size_t)m * d * 8, hipMemcpyDeviceToHost,
-                                       c->stream));
-        }
+        if ((rc = t.z_tail(Zp, ob, mp)) || (rc = t.cprime_tail(X, mp)) || (rc = t.v_tail(Zp, ob, mp))) return rc;
         if ((rc = finish(c))) return rc;
     }
     return finish(c);
@@ -2836,114 +2866,64 @@ int lgs_klein_targets(lgs_ctx* c, uint64_t seed, uint64_t first, int64_t n, cons
 int lgs_klein_decode(lgs_ctx* c, uint64_t seed, uint64_t first, int64_t n, int64_t n_draws,
                      const double* targets, void* z_out, double* v_out, double* cprime_out,
                      const lgs_decode_outputs* out, uint32_t flags) {
-    int rc = check_ctx(c);
+    TargetCall t{c, n, targets, z_out, v_out, cprime_out};
+    int rc = t.open("lgs_klein_decode", flags, kSamplerFlags);
     if (rc) return rc;
-    if (flags & ~(uint32_t)(LGS_DEVICE_PTRS | LGS_Z64 | LGS_COORD_MAJOR | LGS_EXACT_ORDER | LGS_TARGETS_QFRAME))
-        return fail(LGS_ERR_INVALID, "lgs_klein_decode: unsupported flag 0x%x", flags);
     if (n < 0) return fail(LGS_ERR_INVALID, "n < 0");
     if (n_draws < 1 || n_draws > c->max_props)
         return fail(LGS_ERR_INVALID, "n_draws must be 1..max_proposals (%lld)", (long long)c->max_props);
     if (n == 0) return LGS_OK;
-    if (!targets) return fail(LGS_ERR_INVALID, "null targets");
-    const bool dev = flags & LGS_DEVICE_PTRS, z64 = flags & LGS_Z64, cm = flags & LGS_COORD_MAJOR,
-               exact = flags & LGS_EXACT_ORDER, qframe = flags & LGS_TARGETS_QFRAME;
-    if (!qframe && (!c->has_q || c->DQ.bytes < (size_t)c->d * c->d * 8))
-        return fail(LGS_ERR_STATE, "targets in the lattice frame need Q (lgs_set_decoder)");
-    if (v_out && !c->has_B) return fail(LGS_ERR_STATE, "v_out requires B");
+    if ((rc = t.inputs())) return rc;
     const lgs_decode_outputs none{};
     const lgs_decode_outputs& o = out ? *out : none;
-    const int64_t d = c->d, K = n_draws;
-    const int ob = z64 ? 8 : 4;
-    if ((rc = reset_flags(c))) return rc;
+    const int64_t d = t.d, K = n_draws;
+    const int ob = t.ob;
     const int64_t chunk = std::min<int64_t>(n, c->max_props / K);
     const int64_t lanes_p = (chunk * K + 63) / 64 * 64;
     const int64_t ldc = (lanes_p + K - 1) / K;  // >= chunk: the centre columns the lanes read
     const int64_t ldw = (chunk + 63) / 64 * 64;
-    if ((rc = c->CPT.reserve((size_t)ldc * d * 8)) || (rc = c->Z.reserve((size_t)lanes_p * d * ob)) ||
+    if ((rc = t.begin(chunk, ldc)) || (rc = c->Z.reserve((size_t)lanes_p * d * ob)) ||
         (rc = c->DEC_D.reserve((size_t)lanes_p * 8)) || (rc = c->DEC_E.reserve((size_t)lanes_p * 8)) ||
         (rc = c->DEC_WIN.reserve((size_t)chunk * 8)) || (rc = c->DEC_BEST.reserve((size_t)chunk * 8)) ||
         (rc = c->DEC_D2.reserve((size_t)chunk * 8)) || (rc = c->DEC_Z.reserve((size_t)ldw * d * ob)))
         return rc;
-    if (!qframe && ((rc = c->dg_x.reserve((size_t)chunk * d * 8)) || (rc = c->dg_y.reserve((size_t)chunk * d * 8))))
-        return rc;
-    if (!dev) {
-        if ((rc = c->stage_a.reserve((size_t)chunk * d * 8))) return rc;
-        if (cprime_out && (rc = c->stage_b.reserve((size_t)chunk * d * 8))) return rc;
-        if (v_out && (rc = c->V.reserve((size_t)chunk * d * 8))) return rc;
-    }
-    double dmu_scale = 1.0;
-    // test hook (as lgs_klein_targets): a scale s < 1 widens every certificate bound, and
-    // with it every distance bound, by 1 / s
-    if (const char* s = hook("LGS_TEST_Z1CAP_SCALE")) {
-        const double v = atof(s);
-        if (v > 0.0 && v < 1.0) dmu_scale = 1.0 / v;
-    }
+    const double dmu_scale = test_dmu_scale();
     // test hook: the select kernel's path of d > 8192 (coefficients read from the store)
     const bool stage_ok = !hook("LGS_TEST_DECODE_NOSTAGE");
     double* X = c->CPT.as<double>();
     for (int64_t off = 0; off < n; off += chunk) {
-        const int64_t m = std::min<int64_t>(chunk, n - off);
+        const int64_t m = t.chunk_at(off, chunk);
         const int64_t mp = (m * K + 63) / 64 * 64;
-        if ((rc = stage_centres(c, targets, n, off, m, X, ldc, dev, cm, qframe))) return rc;
+        if ((rc = t.centres(X, ldc))) return rc;
         lgs::KleinArgs a = base_args(c, seed);
         a.counter_mode = 0;
         a.base = first + (uint64_t)off * (uint64_t)K;
         a.n = mp;
         a.ldz = mp;
-        void* Zp = c->Z.p;
-        lgs::qkey_drop(c->qkey);  // (written below by another kernel than the Klein launch that keeps it)
+        void* Zp = t.take_store();
         const lgs::DecodeLanes dl{K, c->DEC_D.as<double>(), c->DEC_E.as<double>()};
         {
             Scope s(c, 0);
             c->hist.Z = nullptr;  // (no int16 history: B z reads the compact store)
             HIP_TRY(lgs::launch::klein_decode(a, c->R.as<double>(), c->RP.as<double>(), c->RC.as<double>(), c->panel,
-                                              exact, X, ldc, dmu_scale, ob, Zp, dl, c->stream));
+                                              t.exact, X, ldc, dmu_scale, ob, Zp, dl, c->stream));
         }
-        int64_t* best = dev && o.best_draw ? o.best_draw + off : c->DEC_BEST.as<int64_t>();
-        double* dist2 = dev && o.dist2 ? o.dist2 + off : c->DEC_D2.as<double>();
+        int64_t* best = t.out_ptr(o.best_draw, c->DEC_BEST);
+        double* dist2 = t.out_ptr(o.dist2, c->DEC_D2);
         void* Wp = c->DEC_Z.p;
         {
             Scope s(c, 8);
             HIP_TRY(lgs::launch::decode_select((int)d, m, K, dl.D, dl.E, c->RT.as<double>(), X, ldc, Zp, ob, mp,
                                                c->DEC_WIN.as<int64_t>(), best, dist2, c->flags.as<unsigned int>(),
                                                c->stream, stage_ok));
-            void* zrow = nullptr;  // row-major winners: the caller's device buffer, or staged
-            if (z_out && !cm) zrow = dev ? (char*)z_out + (size_t)off * d * ob : c->stage_a.p;
-            HIP_TRY(lgs::launch::decode_gather((int)d, m, c->DEC_WIN.as<int64_t>(), Zp, ob, mp, Wp, ldw, zrow, d, 1,
-                                               c->stream));
-            if (z_out && cm)
-                HIP_TRY(hipMemcpy2DAsync((char*)z_out + (size_t)off * ob, (size_t)n * ob, Wp, (size_t)ldw * ob,
-                                         (size_t)m * ob, (size_t)d, kind_of(dev, true), c->stream));
-            else if (z_out && !dev)
-                HIP_TRY(hipMemcpyAsync((char*)z_out + (size_t)off * d * ob, zrow, (size_t)m * d * ob,
-                                       hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(lgs::launch::decode_gather((int)d, m, c->DEC_WIN.as<int64_t>(), Zp, ob, mp, Wp, ldw, t.z_rows(), d,
+                                               1, c->stream));
+            if ((rc = t.z_tail(Wp, ob, ldw, true))) return rc;
         }
-        if (!dev) {
-            if (o.best_draw)
-                HIP_TRY(hipMemcpyAsync(o.best_draw + off, best, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
-            if (o.dist2) HIP_TRY(hipMemcpyAsync(o.dist2 + off, dist2, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
-        }
-        if (o.dist2_draws)
-            HIP_TRY(hipMemcpyAsync(o.dist2_draws + (size_t)off * K, dl.D, (size_t)m * K * 8, kind_of(dev, true),
-                                   c->stream));
-        if (o.bound_draws)
-            HIP_TRY(hipMemcpyAsync(o.bound_draws + (size_t)off * K, dl.E, (size_t)m * K * 8, kind_of(dev, true),
-                                   c->stream));
-        if (cprime_out) {  // row-major, the centres the kernel read
-            void* dst = dev ? (void*)(cprime_out + (size_t)off * d) : c->stage_b.p;
-            HIP_TRY(lgs::launch::transpose_out(X, 8, ldc, m, (int)d, dst, 8, c->stream));
-            if (!dev)
-                HIP_TRY(hipMemcpyAsync(cprime_out + (size_t)off * d, dst, (size_t)m * d * 8, hipMemcpyDeviceToHost,
-                                       c->stream));
-        }
-        if (v_out) {
-            double* V = dev ? v_out + (size_t)off * d : c->V.as<double>();
-            if ((rc = run_bz(c, Wp, ob, ldw, m, V))) return rc;
-            if ((rc = settle_bz(c))) return rc;
-            if (!dev)
-                HIP_TRY(hipMemcpyAsync(v_out + (size_t)off * d, V, (size_t)m * d * 8, hipMemcpyDeviceToHost,
-                                       c->stream));
-        }
+        if ((rc = t.out_copy(o.best_draw, best)) || (rc = t.out_copy(o.dist2, dist2)) ||
+            (rc = t.out_copy(o.dist2_draws, dl.D, K)) || (rc = t.out_copy(o.bound_draws, dl.E, K)) ||
+            (rc = t.cprime_tail(X, ldc)) || (rc = t.v_tail(Wp, ob, ldw)))
+            return rc;
         if ((rc = finish(c))) return rc;
     }
     return finish(c);
@@ -2959,63 +2939,44 @@ int lgs_klein_decode(lgs_ctx* c, uint64_t seed, uint64_t first, int64_t n, int64
 int lgs_imhk_targets(lgs_ctx* c, uint64_t seed, uint64_t first_chain, int64_t n, int64_t n_steps,
                      const double* targets, void* z_out, double* v_out, double* cprime_out,
                      const lgs_imhk_targets_outputs* out, uint32_t flags) {
-    int rc = check_ctx(c);
+    TargetCall t{c, n, targets, z_out, v_out, cprime_out};
+    int rc = t.open("lgs_imhk_targets", flags, kSamplerFlags);
     if (rc) return rc;
-    if (flags & ~(uint32_t)(LGS_DEVICE_PTRS | LGS_Z64 | LGS_COORD_MAJOR | LGS_EXACT_ORDER | LGS_TARGETS_QFRAME))
-        return fail(LGS_ERR_INVALID, "lgs_imhk_targets: unsupported flag 0x%x", flags);
     if (n < 0) return fail(LGS_ERR_INVALID, "n < 0");
     if (n_steps < 0 || n_steps >= c->max_props)
         return fail(LGS_ERR_INVALID, "n_steps must be 0..max_proposals - 1 (%lld)", (long long)c->max_props - 1);
     if (first_chain > (1ull << 32) || (uint64_t)n > (1ull << 32) - first_chain)
         return fail(LGS_ERR_INVALID, "first_chain + n exceeds 2^32 (the chain counter has 32 bits)");
     if (n == 0) return LGS_OK;
-    if (!targets) return fail(LGS_ERR_INVALID, "null targets");
-    const bool dev = flags & LGS_DEVICE_PTRS, z64 = flags & LGS_Z64, cm = flags & LGS_COORD_MAJOR,
-               exact = flags & LGS_EXACT_ORDER, qframe = flags & LGS_TARGETS_QFRAME;
-    if (!qframe && (!c->has_q || c->DQ.bytes < (size_t)c->d * c->d * 8))
-        return fail(LGS_ERR_STATE, "targets in the lattice frame need Q (lgs_set_decoder)");
-    if (v_out && !c->has_B) return fail(LGS_ERR_STATE, "v_out requires B");
+    if ((rc = t.inputs())) return rc;
     const lgs_imhk_targets_outputs none{};
     const lgs_imhk_targets_outputs& o = out ? *out : none;
-    const int64_t d = c->d, K = n_steps + 1;
-    const int ob = z64 ? 8 : 4;
-    if ((rc = reset_flags(c))) return rc;
+    const int64_t d = t.d, K = n_steps + 1;
+    const int ob = t.ob;
+    const bool dev = t.dev;
     const int64_t chunk = std::min<int64_t>(n, c->max_props / K);
     const int64_t lanes_p = (chunk * K + 63) / 64 * 64;
     const int64_t ldc = (lanes_p + K - 1) / K;  // >= chunk: the centre columns the lanes read
     const int64_t ldw = (chunk + 63) / 64 * 64;
-    if ((rc = c->CPT.reserve((size_t)ldc * d * 8)) || (rc = c->Z.reserve((size_t)lanes_p * d * ob)) ||
+    if ((rc = t.begin(chunk, ldc)) || (rc = c->Z.reserve((size_t)lanes_p * d * ob)) ||
         (rc = c->LW.reserve((size_t)lanes_p * 8)) || (rc = c->LWE.reserve((size_t)lanes_p * 8)) ||
         (rc = c->DEC_WIN.reserve((size_t)chunk * 8)) || (rc = c->DEC_Z.reserve((size_t)ldw * d * ob)))
         return rc;
-    if (!qframe && ((rc = c->dg_x.reserve((size_t)chunk * d * 8)) || (rc = c->dg_y.reserve((size_t)chunk * d * 8))))
+    if (!dev && ((o.logw && (rc = c->IT_LOGW.reserve((size_t)chunk * 8))) ||
+                 (o.accepts && (rc = c->IT_ACC.reserve((size_t)chunk * 8))) ||
+                 (o.final_step && (rc = c->IT_STEP.reserve((size_t)chunk * 8))) ||
+                 (o.accepted && (rc = c->IT_TRACE.reserve((size_t)chunk * n_steps)))))
         return rc;
-    if (!dev) {
-        if ((rc = c->stage_a.reserve((size_t)chunk * d * 8))) return rc;
-        if (cprime_out && (rc = c->stage_b.reserve((size_t)chunk * d * 8))) return rc;
-        if (v_out && (rc = c->V.reserve((size_t)chunk * d * 8))) return rc;
-        if ((o.logw && (rc = c->IT_LOGW.reserve((size_t)chunk * 8))) ||
-            (o.accepts && (rc = c->IT_ACC.reserve((size_t)chunk * 8))) ||
-            (o.final_step && (rc = c->IT_STEP.reserve((size_t)chunk * 8))) ||
-            (o.accepted && (rc = c->IT_TRACE.reserve((size_t)chunk * n_steps))))
-            return rc;
-    }
-    double dmu_scale = 1.0;
-    // test hook (as lgs_klein_decode): a scale s < 1 widens every certificate bound, and
-    // with it every weight bound, by 1 / s
-    if (const char* s = hook("LGS_TEST_Z1CAP_SCALE")) {
-        const double v = atof(s);
-        if (v > 0.0 && v < 1.0) dmu_scale = 1.0 / v;
-    }
+    const double dmu_scale = test_dmu_scale();
     // test hook (as lgs_imhk): widened weight bounds force the recomputation path on many
     // decisions (clamped to >= 1: a smaller scale would void the certificate)
     const char* bs = hook("LGS_TEST_WL_BOUND_SCALE");
     const double bscale = bs ? std::max(1.0, atof(bs)) : 1.0;
     double* X = c->CPT.as<double>();
     for (int64_t off = 0; off < n; off += chunk) {
-        const int64_t m = std::min<int64_t>(chunk, n - off);
+        const int64_t m = t.chunk_at(off, chunk);
         const int64_t mp = (m * K + 63) / 64 * 64;
-        if ((rc = stage_centres(c, targets, n, off, m, X, ldc, dev, cm, qframe))) return rc;
+        if ((rc = t.centres(X, ldc))) return rc;
         lgs::KleinArgs a = base_args(c, seed);
         a.counter_mode = 1;
         a.chain0 = (uint32_t)(first_chain + (uint64_t)off);
@@ -3025,22 +2986,16 @@ int lgs_imhk_targets(lgs_ctx* c, uint64_t seed, uint64_t first_chain, int64_t n,
         a.ldz = mp;
         a.LW = c->LW.as<double>();
         a.LWE = c->LWE.as<double>();
-        void* Zp = c->Z.p;
-        lgs::qkey_drop(c->qkey);  // (written below by another kernel than the Klein launch that keeps it)
+        void* Zp = t.take_store();
         {
             Scope s(c, 0);
             c->hist.Z = nullptr;  // (no int16 history: B z reads the compact store)
             HIP_TRY(lgs::launch::klein_imhk_targets(a, c->R.as<double>(), c->RP.as<double>(), c->RC.as<double>(),
-                                                    c->panel, exact, X, ldc, dmu_scale, ob, Zp, lgs::WeightLanes{K},
+                                                    c->panel, t.exact, X, ldc, dmu_scale, ob, Zp, lgs::WeightLanes{K},
                                                     c->stream));
         }
         // the sampling kernel's weights and bounds, before the scan replaces recomputed ones
-        if (o.logw_draws)
-            HIP_TRY(hipMemcpyAsync(o.logw_draws + (size_t)off * K, a.LW, (size_t)m * K * 8, kind_of(dev, true),
-                                   c->stream));
-        if (o.bound_draws)
-            HIP_TRY(hipMemcpyAsync(o.bound_draws + (size_t)off * K, a.LWE, (size_t)m * K * 8, kind_of(dev, true),
-                                   c->stream));
+        if ((rc = t.out_copy(o.logw_draws, a.LW, K)) || (rc = t.out_copy(o.bound_draws, a.LWE, K))) return rc;
         lgs::ImhkTargetsArgs aa{};
         aa.nc = m;
         aa.K = K;
@@ -3055,54 +3010,24 @@ int lgs_imhk_targets(lgs_ctx* c, uint64_t seed, uint64_t first_chain, int64_t n,
         aa.CP = X;
         aa.ldc = ldc;
         aa.final_col = c->DEC_WIN.as<int64_t>();
-        aa.logw = !o.logw ? nullptr : dev ? o.logw + off : c->IT_LOGW.as<double>();
-        aa.accepts = !o.accepts ? nullptr : dev ? o.accepts + off : c->IT_ACC.as<int64_t>();
-        aa.final_step = !o.final_step ? nullptr : dev ? o.final_step + off : c->IT_STEP.as<int64_t>();
-        aa.accepted = !o.accepted || n_steps == 0 ? nullptr
-                      : dev                       ? o.accepted + (size_t)off * n_steps
-                                                  : c->IT_TRACE.as<uint8_t>();
+        aa.logw = o.logw ? t.out_ptr(o.logw, c->IT_LOGW) : nullptr;
+        aa.accepts = o.accepts ? t.out_ptr(o.accepts, c->IT_ACC) : nullptr;
+        aa.final_step = o.final_step ? t.out_ptr(o.final_step, c->IT_STEP) : nullptr;
+        aa.accepted = o.accepted && n_steps ? t.out_ptr(o.accepted, c->IT_TRACE, n_steps) : nullptr;
         aa.flagw = c->flags.as<unsigned int>();
         aa.bscale = bscale;
         void* Wp = c->DEC_Z.p;
         {
             Scope s(c, 8);
             HIP_TRY(lgs::launch::imhk_targets_accept(aa, a, c->stream));
-            void* zrow = nullptr;  // row-major final states: the caller's device buffer, or staged
-            if (z_out && !cm) zrow = dev ? (char*)z_out + (size_t)off * d * ob : c->stage_a.p;
-            HIP_TRY(lgs::launch::decode_gather((int)d, m, aa.final_col, Zp, ob, mp, Wp, ldw, zrow, d, 1, c->stream));
-            if (z_out && cm)
-                HIP_TRY(hipMemcpy2DAsync((char*)z_out + (size_t)off * ob, (size_t)n * ob, Wp, (size_t)ldw * ob,
-                                         (size_t)m * ob, (size_t)d, kind_of(dev, true), c->stream));
-            else if (z_out && !dev)
-                HIP_TRY(hipMemcpyAsync((char*)z_out + (size_t)off * d * ob, zrow, (size_t)m * d * ob,
-                                       hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(lgs::launch::decode_gather((int)d, m, aa.final_col, Zp, ob, mp, Wp, ldw, t.z_rows(), d, 1,
+                                               c->stream));
+            if ((rc = t.z_tail(Wp, ob, ldw, true))) return rc;
         }
-        if (!dev) {
-            if (aa.logw) HIP_TRY(hipMemcpyAsync(o.logw + off, aa.logw, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
-            if (aa.accepts)
-                HIP_TRY(hipMemcpyAsync(o.accepts + off, aa.accepts, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
-            if (aa.final_step)
-                HIP_TRY(hipMemcpyAsync(o.final_step + off, aa.final_step, (size_t)m * 8, hipMemcpyDeviceToHost,
-                                       c->stream));
-            if (aa.accepted)
-                HIP_TRY(hipMemcpyAsync(o.accepted + (size_t)off * n_steps, aa.accepted, (size_t)m * n_steps,
-                                       hipMemcpyDeviceToHost, c->stream));
-        }
-        if (cprime_out) {  // row-major, the centres the kernel read
-            void* dst = dev ? (void*)(cprime_out + (size_t)off * d) : c->stage_b.p;
-            HIP_TRY(lgs::launch::transpose_out(X, 8, ldc, m, (int)d, dst, 8, c->stream));
-            if (!dev)
-                HIP_TRY(hipMemcpyAsync(cprime_out + (size_t)off * d, dst, (size_t)m * d * 8, hipMemcpyDeviceToHost,
-                                       c->stream));
-        }
-        if (v_out) {
-            double* V = dev ? v_out + (size_t)off * d : c->V.as<double>();
-            if ((rc = run_bz(c, Wp, ob, ldw, m, V))) return rc;
-            if ((rc = settle_bz(c))) return rc;
-            if (!dev)
-                HIP_TRY(hipMemcpyAsync(v_out + (size_t)off * d, V, (size_t)m * d * 8, hipMemcpyDeviceToHost,
-                                       c->stream));
-        }
+        if ((rc = t.out_copy(o.logw, aa.logw)) || (rc = t.out_copy(o.accepts, aa.accepts)) ||
+            (rc = t.out_copy(o.final_step, aa.final_step)) || (rc = t.out_copy(o.accepted, aa.accepted, n_steps)) ||
+            (rc = t.cprime_tail(X, ldc)) || (rc = t.v_tail(Wp, ob, ldw)))
+            return rc;
         if ((rc = finish(c))) return rc;
     }
     return finish(c);
@@ -3118,10 +3043,9 @@ int lgs_imhk_targets(lgs_ctx* c, uint64_t seed, uint64_t first_chain, int64_t n,
 int lgs_closest_vector(lgs_ctx* c, int64_t n, const double* targets, const double* radius2, int64_t max_nodes,
                        void* z_out, double* v_out, double* cprime_out, const lgs_cvp_outputs* out,
                        uint32_t flags) {
-    int rc = check_ctx(c);
+    TargetCall t{c, n, targets, z_out, v_out, cprime_out};
+    int rc = t.open("lgs_closest_vector", flags, kSamplerFlags & ~(uint32_t)LGS_EXACT_ORDER);
     if (rc) return rc;
-    if (flags & ~(uint32_t)(LGS_DEVICE_PTRS | LGS_Z64 | LGS_COORD_MAJOR | LGS_TARGETS_QFRAME))
-        return fail(LGS_ERR_INVALID, "lgs_closest_vector: unsupported flag 0x%x", flags);
     if (c->d > LGS_CVP_MAX_D)
         return fail(LGS_ERR_INVALID, "lgs_closest_vector: d = %lld > LGS_CVP_MAX_D (%d)", (long long)c->d,
                     LGS_CVP_MAX_D);
@@ -3129,12 +3053,8 @@ int lgs_closest_vector(lgs_ctx* c, int64_t n, const double* targets, const doubl
         return fail(LGS_ERR_INVALID, "max_nodes must be 1..2^40");
     if (n < 0) return fail(LGS_ERR_INVALID, "n < 0");
     if (n == 0) return LGS_OK;
-    if (!targets) return fail(LGS_ERR_INVALID, "null targets");
-    const bool dev = flags & LGS_DEVICE_PTRS, z64 = flags & LGS_Z64, cm = flags & LGS_COORD_MAJOR,
-               qframe = flags & LGS_TARGETS_QFRAME;
-    if (!qframe && (!c->has_q || c->DQ.bytes < (size_t)c->d * c->d * 8))
-        return fail(LGS_ERR_STATE, "targets in the lattice frame need Q (lgs_set_decoder)");
-    if (v_out && !c->has_B) return fail(LGS_ERR_STATE, "v_out requires B");
+    if ((rc = t.inputs())) return rc;
+    const bool dev = t.dev;
     if (radius2) {  // (a device buffer is read back: the check is the host's)
         std::vector<double> rh;
         const double* r = radius2;
@@ -3149,9 +3069,8 @@ int lgs_closest_vector(lgs_ctx* c, int64_t n, const double* targets, const doubl
     }
     const lgs_cvp_outputs none{};
     const lgs_cvp_outputs& o = out ? *out : none;
-    const int64_t d = c->d;
-    const int ob = z64 ? 8 : 4;
-    if ((rc = reset_flags(c))) return rc;
+    const int64_t d = t.d;
+    const int ob = t.ob;
     int64_t slice = lgs::kCvpSlice, slots = lgs::kCvpMaxSlots;
     // (hooks build) LGS_TEST_CVP_SLICE / LGS_TEST_CVP_SLOTS: nodes per lane and launch, lanes
     // per launch (rounded up to whole waves) -- tests suspend and resume every search, and
@@ -3161,27 +3080,20 @@ int lgs_closest_vector(lgs_ctx* c, int64_t n, const double* targets, const doubl
     const int64_t chunk = std::min<int64_t>(n, c->max_props);
     const int64_t ldw = (chunk + 63) / 64 * 64;
     const int64_t S = std::min<int64_t>(ldw, (slots + 63) / 64 * 64);
-    if ((rc = c->CPT.reserve((size_t)ldw * d * 8)) || (rc = c->DEC_Z.reserve((size_t)ldw * d * ob)) ||
+    if ((rc = t.begin(chunk, ldw)) || (rc = c->DEC_Z.reserve((size_t)ldw * d * ob)) ||
         (rc = c->CVP_ST[0].reserve(lgs::cvp_state_bytes((int)d, S))) ||
         (rc = c->CVP_ST[1].reserve(lgs::cvp_state_bytes((int)d, S))) || (rc = c->CVP_CTL.reserve(16)) ||
         (rc = c->CVP_MAP.reserve((size_t)S * 4)) || (rc = c->CVP_D2.reserve((size_t)chunk * 8)) ||
-        (rc = c->CVP_NODES.reserve((size_t)chunk * 8)) || (rc = c->CVP_STATUS.reserve((size_t)chunk * 4)))
+        (rc = c->CVP_NODES.reserve((size_t)chunk * 8)) || (rc = c->CVP_STATUS.reserve((size_t)chunk * 4)) ||
+        (!dev && radius2 && (rc = c->CVP_RAD.reserve((size_t)chunk * 8))))
         return rc;
-    if (!qframe && ((rc = c->dg_x.reserve((size_t)chunk * d * 8)) || (rc = c->dg_y.reserve((size_t)chunk * d * 8))))
-        return rc;
-    if (!dev) {
-        if ((rc = c->stage_a.reserve((size_t)chunk * d * 8))) return rc;
-        if (cprime_out && (rc = c->stage_b.reserve((size_t)chunk * d * 8))) return rc;
-        if (v_out && (rc = c->V.reserve((size_t)chunk * d * 8))) return rc;
-        if (radius2 && (rc = c->CVP_RAD.reserve((size_t)chunk * 8))) return rc;
-    }
     const lgs::CvpState st[2] = {lgs::cvp_state_at(c->CVP_ST[0].p, (int)d, S),
                                  lgs::cvp_state_at(c->CVP_ST[1].p, (int)d, S)};
     double* X = c->CPT.as<double>();
     std::vector<int32_t> tgt_h, map_h;
     for (int64_t off = 0; off < n; off += chunk) {
-        const int64_t m = std::min<int64_t>(chunk, n - off);
-        if ((rc = stage_centres(c, targets, n, off, m, X, ldw, dev, cm, qframe))) return rc;
+        const int64_t m = t.chunk_at(off, chunk);
+        if ((rc = t.centres(X, ldw))) return rc;
         lgs::CvpArgs a{};
         a.d = (int)d;
         a.m = m;
@@ -3203,9 +3115,9 @@ int lgs_closest_vector(lgs_ctx* c, int64_t n, const double* targets, const doubl
         a.ctl = c->CVP_CTL.as<unsigned long long>();
         a.W = c->DEC_Z.p;
         a.ldw = ldw;
-        a.dist2 = dev && o.dist2 ? o.dist2 + off : c->CVP_D2.as<double>();
-        a.nodes = dev && o.nodes ? o.nodes + off : c->CVP_NODES.as<int64_t>();
-        a.status = dev && o.status ? o.status + off : c->CVP_STATUS.as<int32_t>();
+        a.dist2 = t.out_ptr(o.dist2, c->CVP_D2);
+        a.nodes = t.out_ptr(o.nodes, c->CVP_NODES);
+        a.status = t.out_ptr(o.status, c->CVP_STATUS);
         a.flags = c->flags.as<unsigned int>();
         // (columns m .. ldw - 1 of the compact store stay zero for B z)
         HIP_TRY(hipMemsetAsync(a.W, 0, (size_t)ldw * d * ob, c->stream));
@@ -3254,39 +3166,9 @@ int lgs_closest_vector(lgs_ctx* c, int64_t n, const double* targets, const doubl
         }
         void* Wp = a.W;
         c->hist.Z = nullptr;  // (no int16 history: B z reads the compact store)
-        if (z_out) {
-            if (cm) {
-                HIP_TRY(hipMemcpy2DAsync((char*)z_out + (size_t)off * ob, (size_t)n * ob, Wp, (size_t)ldw * ob,
-                                         (size_t)m * ob, (size_t)d, kind_of(dev, true), c->stream));
-            } else {
-                void* dst = dev ? (char*)z_out + (size_t)off * d * ob : c->stage_a.p;
-                HIP_TRY(lgs::launch::transpose_out(Wp, ob, ldw, m, (int)d, dst, ob, c->stream));
-                if (!dev)
-                    HIP_TRY(hipMemcpyAsync((char*)z_out + (size_t)off * d * ob, dst, (size_t)m * d * ob,
-                                           hipMemcpyDeviceToHost, c->stream));
-            }
-        }
-        if (!dev) {
-            if (o.dist2) HIP_TRY(hipMemcpyAsync(o.dist2 + off, a.dist2, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
-            if (o.nodes) HIP_TRY(hipMemcpyAsync(o.nodes + off, a.nodes, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
-            if (o.status)
-                HIP_TRY(hipMemcpyAsync(o.status + off, a.status, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
-        }
-        if (cprime_out) {  // row-major, the centres the kernel read
-            void* dst = dev ? (void*)(cprime_out + (size_t)off * d) : c->stage_b.p;
-            HIP_TRY(lgs::launch::transpose_out(X, 8, ldw, m, (int)d, dst, 8, c->stream));
-            if (!dev)
-                HIP_TRY(hipMemcpyAsync(cprime_out + (size_t)off * d, dst, (size_t)m * d * 8, hipMemcpyDeviceToHost,
-                                       c->stream));
-        }
-        if (v_out) {
-            double* V = dev ? v_out + (size_t)off * d : c->V.as<double>();
-            if ((rc = run_bz(c, Wp, ob, ldw, m, V))) return rc;
-            if ((rc = settle_bz(c))) return rc;
-            if (!dev)
-                HIP_TRY(hipMemcpyAsync(v_out + (size_t)off * d, V, (size_t)m * d * 8, hipMemcpyDeviceToHost,
-                                       c->stream));
-        }
+        if ((rc = t.z_tail(Wp, ob, ldw)) || (rc = t.out_copy(o.dist2, a.dist2)) || (rc = t.out_copy(o.nodes, a.nodes)) ||
+            (rc = t.out_copy(o.status, a.status)) || (rc = t.cprime_tail(X, ldw)) || (rc = t.v_tail(Wp, ob, ldw)))
+            return rc;
         if ((rc = finish(c))) return rc;
     }
     return finish(c);

@@ -3798,29 +3798,46 @@ hipError_t nearest_plane(int d, int64_t n, int panel, const double* RP, const do
     return hipGetLastError();
 }
 
+// The one launch of the per-target sampling kernels: LO is the lanes' trailing output
+// argument -- none (lgs_klein_targets), DecodeLanes or WeightLanes -- and names the
+// exact-order kernel; the certified kernel is klein_targets_kernel<ZT, PB, LO...>.
+template <typename ZT, typename... LO>
+static hipError_t klein_targets_zt(const KleinArgs& a, const double* R, const double* RP, const double* RC,
+                                   int panel, bool exact, const double* CP, int64_t ldc, double dmu_scale, ZT* Z,
+                                   hipStream_t st, const LO&... lo) {
+    const dim3 grid((unsigned)((a.n + 255) / 256));
+    if (exact) {
+        if constexpr (sizeof...(LO) == 0)
+            hipLaunchKernelGGL(klein_targets_exact_kernel<ZT>, grid, dim3(256), 0, st, a, R, CP, ldc, Z);
+        else if constexpr ((std::is_same<LO, DecodeLanes>::value || ...))
+            hipLaunchKernelGGL(klein_decode_exact_kernel<ZT>, grid, dim3(256), 0, st, a, R, CP, ldc, Z, lo...);
+        else
+            hipLaunchKernelGGL(klein_imhk_exact_kernel<ZT>, grid, dim3(256), 0, st, a, R, CP, ldc, Z, lo...);
+        return hipGetLastError();
+    }
+    if (a.n % 64 != 0 || a.ldz % 4 != 0 || ((uintptr_t)Z % 16) != 0) return hipErrorInvalidValue;
+    if (panel == 16)
+        hipLaunchKernelGGL((klein_targets_kernel<ZT, 16, LO...>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, Z, lo...);
+    else
+        hipLaunchKernelGGL((klein_targets_kernel<ZT, 32, LO...>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, Z, lo...);
+    return hipGetLastError();
+}
+
+// (the store is int32 or int64: LGS_ZT would instantiate int16 kernels nobody launches)
+template <typename... LO>
+static hipError_t klein_targets_any(const KleinArgs& a, const double* R, const double* RP, const double* RC,
+                                    int panel, bool exact, const double* CP, int64_t ldc, double dmu_scale, int zb,
+                                    void* Z, hipStream_t st, const LO&... lo) {
+    if (zb == 4) return klein_targets_zt(a, R, RP, RC, panel, exact, CP, ldc, dmu_scale, (int32_t*)Z, st, lo...);
+    return klein_targets_zt(a, R, RP, RC, panel, exact, CP, ldc, dmu_scale, (int64_t*)Z, st, lo...);
+}
+
 hipError_t klein_targets(const KleinArgs& a, const double* R, const double* RP, const double* RC, int panel,
                          bool exact, const double* CP, int64_t ldc, double dmu_scale, int zb, void* Z,
                          hipStream_t st) {
     if (a.n <= 0) return hipSuccess;
     if (zb != 4 && zb != 8) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((a.n + 255) / 256));
-    if (exact) {
-        if (zb == 4)
-            hipLaunchKernelGGL(klein_targets_exact_kernel<int32_t>, grid, dim3(256), 0, st, a, R, CP, ldc, (int32_t*)Z);
-        else
-            hipLaunchKernelGGL(klein_targets_exact_kernel<int64_t>, grid, dim3(256), 0, st, a, R, CP, ldc, (int64_t*)Z);
-        return hipGetLastError();
-    }
-    if (a.n % 64 != 0 || a.ldz % 4 != 0 || ((uintptr_t)Z % 16) != 0) return hipErrorInvalidValue;
-    if (panel == 16 && zb == 4)
-        hipLaunchKernelGGL((klein_targets_kernel<int32_t, 16>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int32_t*)Z);
-    else if (panel == 16)
-        hipLaunchKernelGGL((klein_targets_kernel<int64_t, 16>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int64_t*)Z);
-    else if (zb == 4)
-        hipLaunchKernelGGL((klein_targets_kernel<int32_t, 32>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int32_t*)Z);
-    else
-        hipLaunchKernelGGL((klein_targets_kernel<int64_t, 32>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int64_t*)Z);
-    return hipGetLastError();
+    return klein_targets_any(a, R, RP, RC, panel, exact, CP, ldc, dmu_scale, zb, Z, st);
 }
 
 hipError_t klein_decode(const KleinArgs& a, const double* R, const double* RP, const double* RC, int panel,
@@ -3828,24 +3845,7 @@ hipError_t klein_decode(const KleinArgs& a, const double* R, const double* RP, c
                         const DecodeLanes& dl, hipStream_t st) {
     if (a.n <= 0) return hipSuccess;
     if ((zb != 4 && zb != 8) || dl.K < 1 || !dl.D || !dl.E) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((a.n + 255) / 256));
-    if (exact) {
-        if (zb == 4)
-            hipLaunchKernelGGL(klein_decode_exact_kernel<int32_t>, grid, dim3(256), 0, st, a, R, CP, ldc, (int32_t*)Z, dl);
-        else
-            hipLaunchKernelGGL(klein_decode_exact_kernel<int64_t>, grid, dim3(256), 0, st, a, R, CP, ldc, (int64_t*)Z, dl);
-        return hipGetLastError();
-    }
-    if (a.n % 64 != 0 || a.ldz % 4 != 0 || ((uintptr_t)Z % 16) != 0) return hipErrorInvalidValue;
-    if (panel == 16 && zb == 4)
-        hipLaunchKernelGGL((klein_targets_kernel<int32_t, 16, DecodeLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int32_t*)Z, dl);
-    else if (panel == 16)
-        hipLaunchKernelGGL((klein_targets_kernel<int64_t, 16, DecodeLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int64_t*)Z, dl);
-    else if (zb == 4)
-        hipLaunchKernelGGL((klein_targets_kernel<int32_t, 32, DecodeLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int32_t*)Z, dl);
-    else
-        hipLaunchKernelGGL((klein_targets_kernel<int64_t, 32, DecodeLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int64_t*)Z, dl);
-    return hipGetLastError();
+    return klein_targets_any(a, R, RP, RC, panel, exact, CP, ldc, dmu_scale, zb, Z, st, dl);
 }
 
 hipError_t klein_imhk_targets(const KleinArgs& a, const double* R, const double* RP, const double* RC, int panel,
@@ -3854,24 +3854,7 @@ hipError_t klein_imhk_targets(const KleinArgs& a, const double* R, const double*
     if (a.n <= 0) return hipSuccess;
     if ((zb != 4 && zb != 8) || wl.K < 1 || !a.LW || !a.LWE || a.counter_mode != 1 || a.nt != wl.K)
         return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((a.n + 255) / 256));
-    if (exact) {
-        if (zb == 4)
-            hipLaunchKernelGGL(klein_imhk_exact_kernel<int32_t>, grid, dim3(256), 0, st, a, R, CP, ldc, (int32_t*)Z, wl);
-        else
-            hipLaunchKernelGGL(klein_imhk_exact_kernel<int64_t>, grid, dim3(256), 0, st, a, R, CP, ldc, (int64_t*)Z, wl);
-        return hipGetLastError();
-    }
-    if (a.n % 64 != 0 || a.ldz % 4 != 0 || ((uintptr_t)Z % 16) != 0) return hipErrorInvalidValue;
-    if (panel == 16 && zb == 4)
-        hipLaunchKernelGGL((klein_targets_kernel<int32_t, 16, WeightLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int32_t*)Z, wl);
-    else if (panel == 16)
-        hipLaunchKernelGGL((klein_targets_kernel<int64_t, 16, WeightLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int64_t*)Z, wl);
-    else if (zb == 4)
-        hipLaunchKernelGGL((klein_targets_kernel<int32_t, 32, WeightLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int32_t*)Z, wl);
-    else
-        hipLaunchKernelGGL((klein_targets_kernel<int64_t, 32, WeightLanes>), grid, dim3(256), 0, st, a, RP, RC, CP, ldc, dmu_scale, (int64_t*)Z, wl);
-    return hipGetLastError();
+    return klein_targets_any(a, R, RP, RC, panel, exact, CP, ldc, dmu_scale, zb, Z, st, wl);
 }
 
 hipError_t imhk_targets_accept(const ImhkTargetsArgs& a, const KleinArgs& ka, hipStream_t st) {

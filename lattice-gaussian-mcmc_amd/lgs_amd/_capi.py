@@ -255,6 +255,30 @@ def _check_padded(x, shape, ld):
         raise ValueError(f"buffer of {have} elements does not hold shape {shape} at leading dimension {ld}")
 
 
+def _outputs(struct, *arrays):
+    """ctypes.byref of `struct` filled with the arrays' addresses in field order, or None when
+    every one is None (the library takes a null outputs pointer)."""
+    if all(a is None for a in arrays):
+        return None
+    return ctypes.byref(struct(*(None if a is None else _ptr(a).value for a in arrays)))
+
+
+def _host_retry(flags, call):
+    """The *_host methods' width loop: call(flags, z_dtype) with int32 coefficients (int64 at
+    once with LGS_Z64 in flags), and once more with LGS_Z64 after LGS_ERR_OVERFLOW."""
+    for z64 in (bool(flags & LGS_Z64), True):
+        try:
+            return call(flags | (LGS_Z64 if z64 else 0), np.int64 if z64 else np.int32)
+        except LgsError as e:
+            if e.code != LGS_ERR_OVERFLOW or z64:
+                raise
+    raise AssertionError("unreachable")
+
+
+def _z64(z):
+    return None if z is None else z.astype(np.int64, copy=False)
+
+
 def x_flags(a) -> int:
     """LGS_X_* element-type flag of a host array / device tensor (fp64, int32, int64)."""
     t = _dtype_name(a)
@@ -435,40 +459,57 @@ class Context:
         self._ck(self._L.lgs_set_decoder(self._h, _ptr(Qc), _ptr(Bi)))
         self._keep_dec = (Qc, Bi)
 
+    def _n_targets(self, targets, flags):
+        """n of targets (n, d), or (d, n) with LGS_COORD_MAJOR; no library call."""
+        cm = bool(flags & LGS_COORD_MAJOR)
+        if len(targets.shape) != 2 or targets.shape[0 if cm else 1] != self.d:
+            raise ValueError(f"targets must be (n, {self.d}), or ({self.d}, n) with LGS_COORD_MAJOR")
+        return int(targets.shape[1] if cm else targets.shape[0])
+
+    def _check_target_bufs(self, flags, targets, z_out, v_out, cprime_out, *more):
+        """_check_bufs of the buffers every per-target call has, and of `more`."""
+        zt = "int64" if flags & LGS_Z64 else "int32"
+        _check_bufs(flags, self.device, ((targets, "float64", "targets"), (z_out, zt, "z_out"),
+                                         (v_out, "float64", "v_out"), (cprime_out, "float64", "cprime_out")) + more)
+
+    def _host_targets(self, targets, flags, name):
+        """Row-major host targets (n, d) of a *_host method."""
+        if flags & (LGS_DEVICE_PTRS | LGS_COORD_MAJOR):
+            raise ValueError(f"{name} takes row-major host targets")
+        t = np.ascontiguousarray(targets, dtype=np.float64)
+        if t.ndim != 2 or t.shape[1] != self.d:
+            raise ValueError(f"targets must be (n, {self.d})")
+        return t
+
+    def _host_zvc(self, n, zdt, want_z, want_v, want_cprime):
+        """Fresh z / v / c' arrays of a *_host method (None where not wanted)."""
+        return (np.empty((n, self.d), dtype=zdt) if want_z else None, np.empty((n, self.d)) if want_v else None,
+                np.empty((n, self.d)) if want_cprime else None)
+
     def decode(self, targets, method="plane", z_out=None, v_out=None, flags=0):
         """Raw lgs_nearest_plane / lgs_round_decode on caller buffers (numpy host or device
         tensors).  targets is float64 (n, d), or (d, n) with LGS_COORD_MAJOR; z_out has the
         same layout, int32 or int64 per LGS_Z64; v_out is float64 (n, d)."""
         if method not in ("plane", "round"):
             raise ValueError("method is 'plane' or 'round'")
+        n = self._n_targets(targets, flags)
         cm = bool(flags & LGS_COORD_MAJOR)
-        if len(targets.shape) != 2 or targets.shape[0 if cm else 1] != self.d:
-            raise ValueError(f"targets must be (n, {self.d}), or ({self.d}, n) with LGS_COORD_MAJOR")
-        n = targets.shape[1] if cm else targets.shape[0]
-        zt = "int64" if flags & LGS_Z64 else "int32"
-        _check_bufs(flags, self.device, ((targets, "float64", "targets"), (z_out, zt, "z_out"),
-                                         (v_out, "float64", "v_out")))
+        self._check_target_bufs(flags, targets, z_out, v_out, None)
         for a, want, name in ((z_out, (self.d, n) if cm else (n, self.d), "z_out"), (v_out, (n, self.d), "v_out")):
             if a is not None and not isinstance(a, int) and tuple(a.shape) != want:
                 raise ValueError(f"{name}: expected shape {want}, got {tuple(a.shape)}")
         fn = self._L.lgs_nearest_plane if method == "plane" else self._L.lgs_round_decode
-        self._ck(fn(self._h, int(n), _ptr(targets), _ptr(z_out), _ptr(v_out), int(flags)))
+        self._ck(fn(self._h, n, _ptr(targets), _ptr(z_out), _ptr(v_out), int(flags)))
 
     def decode_host(self, targets, method="plane", want_v=True):
         """Decode host targets (n x d); int32 coefficients first, int64 on overflow."""
         t = np.ascontiguousarray(targets, dtype=np.float64)
-        n = t.shape[0]
-        for z64 in (False, True):
-            z = np.empty((n, self.d), dtype=np.int64 if z64 else np.int32)
-            v = np.empty((n, self.d)) if want_v else None
-            try:
-                self.decode(t, method, z, v, LGS_Z64 if z64 else 0)
-            except LgsError as e:
-                if e.code == LGS_ERR_OVERFLOW and not z64:
-                    continue
-                raise
-            return z.astype(np.int64, copy=False), v
-        raise AssertionError("unreachable")
+
+        def call(f, zdt):
+            z, v, _ = self._host_zvc(t.shape[0], zdt, True, want_v, False)
+            self.decode(t, method, z, v, f)
+            return _z64(z), v
+        return _host_retry(0, call)
 
     # ---------------------------------------------------------------- per-sample centres
     def klein_targets(self, seed, first, targets, z_out=None, v_out=None, cprime_out=None, flags=0):
@@ -476,13 +517,9 @@ class Context:
         draw around each target, sample k on the counters of Klein sample first + k.
         targets is (n, d), or (d, n) with LGS_COORD_MAJOR; with LGS_TARGETS_QFRAME it holds
         c' = Q^T t already."""
-        if len(targets.shape) != 2 or targets.shape[0 if flags & LGS_COORD_MAJOR else 1] != self.d:
-            raise ValueError(f"targets must be (n, {self.d}), or ({self.d}, n) with LGS_COORD_MAJOR")
-        n = targets.shape[1] if flags & LGS_COORD_MAJOR else targets.shape[0]
-        zt = "int64" if flags & LGS_Z64 else "int32"
-        _check_bufs(flags, self.device, ((targets, "float64", "targets"), (z_out, zt, "z_out"),
-                                         (v_out, "float64", "v_out"), (cprime_out, "float64", "cprime_out")))
-        self._ck(self._L.lgs_klein_targets(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(n),
+        n = self._n_targets(targets, flags)
+        self._check_target_bufs(flags, targets, z_out, v_out, cprime_out)
+        self._ck(self._L.lgs_klein_targets(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), n,
                                            _ptr(targets), _ptr(z_out), _ptr(v_out), _ptr(cprime_out),
                                            int(flags)))
 
@@ -490,25 +527,13 @@ class Context:
                            flags=0):
         """Klein draws around host targets (n, d) into fresh host arrays {"z", "v", "cprime"};
         int32 coefficients first, int64 on overflow (same draws: fixed counters)."""
-        if flags & (LGS_DEVICE_PTRS | LGS_COORD_MAJOR):
-            raise ValueError("klein_targets_host takes row-major host targets")
-        t = np.ascontiguousarray(targets, dtype=np.float64)
-        if t.ndim != 2 or t.shape[1] != self.d:
-            raise ValueError(f"targets must be (n, {self.d})")
-        n = t.shape[0]
-        for z64 in (bool(flags & LGS_Z64), True):
-            f = flags | (LGS_Z64 if z64 else 0)
-            z = np.empty((n, self.d), dtype=np.int64 if z64 else np.int32) if want_z else None
-            v = np.empty((n, self.d)) if want_v else None
-            cp = np.empty((n, self.d)) if want_cprime else None
-            try:
-                self.klein_targets(seed, first, t, z, v, cp, f)
-            except LgsError as e:
-                if e.code == LGS_ERR_OVERFLOW and not z64:
-                    continue
-                raise
-            return {"z": None if z is None else z.astype(np.int64, copy=False), "v": v, "cprime": cp}
-        raise AssertionError("unreachable")
+        t = self._host_targets(targets, flags, "klein_targets_host")
+
+        def call(f, zdt):
+            z, v, cp = self._host_zvc(t.shape[0], zdt, want_z, want_v, want_cprime)
+            self.klein_targets(seed, first, t, z, v, cp, f)
+            return {"z": _z64(z), "v": v, "cprime": cp}
+        return _host_retry(flags, call)
 
     # ---------------------------------------------------------------- decoding by sampling
     def klein_decode(self, seed, first, targets, n_draws, z_out=None, v_out=None, cprime_out=None,
@@ -517,22 +542,13 @@ class Context:
         of n_draws Klein draws around each target; draw k of target t is on the counters of
         Klein sample first + t * n_draws + k.  targets as in klein_targets; best_draw (n,)
         int64, dist2 (n,), dist2_draws / bound_draws (n, n_draws) float64, all optional."""
-        if len(targets.shape) != 2 or targets.shape[0 if flags & LGS_COORD_MAJOR else 1] != self.d:
-            raise ValueError(f"targets must be (n, {self.d}), or ({self.d}, n) with LGS_COORD_MAJOR")
-        n = targets.shape[1] if flags & LGS_COORD_MAJOR else targets.shape[0]
-        zt = "int64" if flags & LGS_Z64 else "int32"
-        _check_bufs(flags, self.device, ((targets, "float64", "targets"), (z_out, zt, "z_out"),
-                                         (v_out, "float64", "v_out"), (cprime_out, "float64", "cprime_out"),
-                                         (best_draw, "int64", "best_draw"), (dist2, "float64", "dist2"),
-                                         (dist2_draws, "float64", "dist2_draws"),
-                                         (bound_draws, "float64", "bound_draws")))
-        out = None
-        if not (best_draw is None and dist2 is None and dist2_draws is None and bound_draws is None):
-            out = DecodeOutputs(*(None if a is None else _ptr(a).value
-                                  for a in (best_draw, dist2, dist2_draws, bound_draws)))
-        self._ck(self._L.lgs_klein_decode(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(n),
-                                          int(n_draws), _ptr(targets), _ptr(z_out), _ptr(v_out),
-                                          _ptr(cprime_out), None if out is None else ctypes.byref(out),
+        n = self._n_targets(targets, flags)
+        self._check_target_bufs(flags, targets, z_out, v_out, cprime_out,
+                                (best_draw, "int64", "best_draw"), (dist2, "float64", "dist2"),
+                                (dist2_draws, "float64", "dist2_draws"), (bound_draws, "float64", "bound_draws"))
+        self._ck(self._L.lgs_klein_decode(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), n, int(n_draws),
+                                          _ptr(targets), _ptr(z_out), _ptr(v_out), _ptr(cprime_out),
+                                          _outputs(DecodeOutputs, best_draw, dist2, dist2_draws, bound_draws),
                                           int(flags)))
 
     def klein_decode_host(self, seed, first, targets, n_draws, *, want_z=True, want_v=True, want_cprime=False,
@@ -540,35 +556,23 @@ class Context:
         """Decoding by sampling on host targets (n, d) into fresh host arrays {"z", "v",
         "cprime", "best_draw", "dist2"} (and "dist2_draws", "bound_draws" with want_draws);
         int32 coefficients first, int64 on overflow (same draws: fixed counters)."""
-        if flags & (LGS_DEVICE_PTRS | LGS_COORD_MAJOR):
-            raise ValueError("klein_decode_host takes row-major host targets")
-        t = np.ascontiguousarray(targets, dtype=np.float64)
-        if t.ndim != 2 or t.shape[1] != self.d:
-            raise ValueError(f"targets must be (n, {self.d})")
+        t = self._host_targets(targets, flags, "klein_decode_host")
         K = int(n_draws)
         if K < 1:
             raise ValueError("n_draws must be >= 1")
         n = t.shape[0]
-        for z64 in (bool(flags & LGS_Z64), True):
-            f = flags | (LGS_Z64 if z64 else 0)
-            z = np.empty((n, self.d), dtype=np.int64 if z64 else np.int32) if want_z else None
-            v = np.empty((n, self.d)) if want_v else None
-            cp = np.empty((n, self.d)) if want_cprime else None
+
+        def call(f, zdt):
+            z, v, cp = self._host_zvc(n, zdt, want_z, want_v, want_cprime)
             best, d2 = np.empty(n, dtype=np.int64), np.empty(n)
             dd = np.empty((n, K)) if want_draws else None
             bd = np.empty((n, K)) if want_draws else None
-            try:
-                self.klein_decode(seed, first, t, K, z, v, cp, best, d2, dd, bd, f)
-            except LgsError as e:
-                if e.code == LGS_ERR_OVERFLOW and not z64:
-                    continue
-                raise
-            r = {"z": None if z is None else z.astype(np.int64, copy=False), "v": v, "cprime": cp,
-                 "best_draw": best, "dist2": d2}
+            self.klein_decode(seed, first, t, K, z, v, cp, best, d2, dd, bd, f)
+            r = {"z": _z64(z), "v": v, "cprime": cp, "best_draw": best, "dist2": d2}
             if want_draws:
                 r["dist2_draws"], r["bound_draws"] = dd, bd
             return r
-        raise AssertionError("unreachable")
+        return _host_retry(flags, call)
 
     # ---------------------------------------------------------------- IMHK around per-target centres
     def imhk_targets(self, seed, first_chain, targets, n_steps, z_out=None, v_out=None, cprime_out=None,
@@ -579,23 +583,15 @@ class Context:
         first_chain + k, its draw t on the counters (chain, step t).  targets as in
         klein_targets; logw (n,) float64, accepts / final_step (n,) int64, accepted
         (n, n_steps) uint8, logw_draws / bound_draws (n, n_steps + 1) float64, all optional."""
-        if len(targets.shape) != 2 or targets.shape[0 if flags & LGS_COORD_MAJOR else 1] != self.d:
-            raise ValueError(f"targets must be (n, {self.d}), or ({self.d}, n) with LGS_COORD_MAJOR")
-        n = targets.shape[1] if flags & LGS_COORD_MAJOR else targets.shape[0]
-        zt = "int64" if flags & LGS_Z64 else "int32"
-        outs = (logw, accepts, final_step, accepted, logw_draws, bound_draws)
-        _check_bufs(flags, self.device, ((targets, "float64", "targets"), (z_out, zt, "z_out"),
-                                         (v_out, "float64", "v_out"), (cprime_out, "float64", "cprime_out"),
-                                         (logw, "float64", "logw"), (accepts, "int64", "accepts"),
-                                         (final_step, "int64", "final_step"), (accepted, "uint8", "accepted"),
-                                         (logw_draws, "float64", "logw_draws"),
-                                         (bound_draws, "float64", "bound_draws")))
-        out = None
-        if any(a is not None for a in outs):
-            out = ImhkTargetsOutputs(*(None if a is None else _ptr(a).value for a in outs))
-        self._ck(self._L.lgs_imhk_targets(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_chain), int(n),
-                                          int(n_steps), _ptr(targets), _ptr(z_out), _ptr(v_out),
-                                          _ptr(cprime_out), None if out is None else ctypes.byref(out),
+        n = self._n_targets(targets, flags)
+        self._check_target_bufs(flags, targets, z_out, v_out, cprime_out,
+                                (logw, "float64", "logw"), (accepts, "int64", "accepts"),
+                                (final_step, "int64", "final_step"), (accepted, "uint8", "accepted"),
+                                (logw_draws, "float64", "logw_draws"), (bound_draws, "float64", "bound_draws"))
+        self._ck(self._L.lgs_imhk_targets(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_chain), n, int(n_steps),
+                                          _ptr(targets), _ptr(z_out), _ptr(v_out), _ptr(cprime_out),
+                                          _outputs(ImhkTargetsOutputs, logw, accepts, final_step, accepted,
+                                                   logw_draws, bound_draws),
                                           int(flags)))
 
     def imhk_targets_host(self, seed, first_chain, targets, n_steps, *, want_z=True, want_v=True,
@@ -603,36 +599,24 @@ class Context:
         """IMHK chains around host targets (n, d) into fresh host arrays {"z", "v", "cprime",
         "logw", "accepts", "final_step"} (and "accepted", "logw_draws", "bound_draws" with
         want_trace); int32 coefficients first, int64 on overflow (same draws: fixed counters)."""
-        if flags & (LGS_DEVICE_PTRS | LGS_COORD_MAJOR):
-            raise ValueError("imhk_targets_host takes row-major host targets")
-        t = np.ascontiguousarray(targets, dtype=np.float64)
-        if t.ndim != 2 or t.shape[1] != self.d:
-            raise ValueError(f"targets must be (n, {self.d})")
+        t = self._host_targets(targets, flags, "imhk_targets_host")
         T = int(n_steps)
         if T < 0:
             raise ValueError("n_steps must be >= 0")
         n = t.shape[0]
-        for z64 in (bool(flags & LGS_Z64), True):
-            f = flags | (LGS_Z64 if z64 else 0)
-            z = np.empty((n, self.d), dtype=np.int64 if z64 else np.int32) if want_z else None
-            v = np.empty((n, self.d)) if want_v else None
-            cp = np.empty((n, self.d)) if want_cprime else None
+
+        def call(f, zdt):
+            z, v, cp = self._host_zvc(n, zdt, want_z, want_v, want_cprime)
             lw, acc, fs = np.empty(n), np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
             tr = np.empty((n, T), dtype=np.uint8) if want_trace else None
             ld = np.empty((n, T + 1)) if want_trace else None
             bd = np.empty((n, T + 1)) if want_trace else None
-            try:
-                self.imhk_targets(seed, first_chain, t, T, z, v, cp, lw, acc, fs, tr, ld, bd, f)
-            except LgsError as e:
-                if e.code == LGS_ERR_OVERFLOW and not z64:
-                    continue
-                raise
-            r = {"z": None if z is None else z.astype(np.int64, copy=False), "v": v, "cprime": cp,
-                 "logw": lw, "accepts": acc, "final_step": fs}
+            self.imhk_targets(seed, first_chain, t, T, z, v, cp, lw, acc, fs, tr, ld, bd, f)
+            r = {"z": _z64(z), "v": v, "cprime": cp, "logw": lw, "accepts": acc, "final_step": fs}
             if want_trace:
                 r["accepted"], r["logw_draws"], r["bound_draws"] = tr, ld, bd
             return r
-        raise AssertionError("unreachable")
+        return _host_retry(flags, call)
 
     # ---------------------------------------------------------------- exact closest vector
     _CVP_FLAGS = LGS_DEVICE_PTRS | LGS_Z64 | LGS_COORD_MAJOR | LGS_TARGETS_QFRAME
@@ -646,10 +630,7 @@ class Context:
         if isinstance(max_nodes, bool) or not isinstance(max_nodes, (int, np.integer)) or \
                 not 1 <= max_nodes <= 1 << 40:
             raise ValueError(f"max_nodes must be an integer in 1..2^40, got {max_nodes!r}")
-        cm = bool(flags & LGS_COORD_MAJOR)
-        if len(targets.shape) != 2 or targets.shape[0 if cm else 1] != self.d:
-            raise ValueError(f"targets must be (n, {self.d}), or ({self.d}, n) with LGS_COORD_MAJOR")
-        return int(targets.shape[1] if cm else targets.shape[0])
+        return self._n_targets(targets, flags)
 
     def closest_vector(self, targets, max_nodes, radius2=None, z_out=None, v_out=None, cprime_out=None,
                        dist2=None, nodes=None, status=None, flags=0):
@@ -670,12 +651,9 @@ class Context:
                               (dist2, (n,), "dist2"), (nodes, (n,), "nodes"), (status, (n,), "status")):
             if a is not None and not isinstance(a, int) and tuple(a.shape) != want:
                 raise ValueError(f"{name}: expected shape {want}, got {tuple(a.shape)}")
-        out = None
-        if not (dist2 is None and nodes is None and status is None):
-            out = CvpOutputs(*(None if a is None else _ptr(a).value for a in (dist2, nodes, status)))
         self._ck(self._L.lgs_closest_vector(self._h, n, _ptr(targets), _ptr(radius2), int(max_nodes), _ptr(z_out),
                                             _ptr(v_out), _ptr(cprime_out),
-                                            None if out is None else ctypes.byref(out), int(flags)))
+                                            _outputs(CvpOutputs, dist2, nodes, status), int(flags)))
 
     def closest_vector_host(self, targets, max_nodes, radius2=None, *, want_z=True, want_v=True,
                             want_cprime=False, flags=0):
@@ -691,21 +669,13 @@ class Context:
             r2 = np.ascontiguousarray(radius2, dtype=np.float64)
             if r2.shape != (n,) or not np.all(r2 >= 0):
                 raise ValueError(f"radius2 must hold {n} non-negative values")
-        for z64 in (bool(flags & LGS_Z64), True):
-            f = flags | (LGS_Z64 if z64 else 0)
-            z = np.empty((n, self.d), dtype=np.int64 if z64 else np.int32) if want_z else None
-            v = np.empty((n, self.d)) if want_v else None
-            cp = np.empty((n, self.d)) if want_cprime else None
+
+        def call(f, zdt):
+            z, v, cp = self._host_zvc(n, zdt, want_z, want_v, want_cprime)
             d2, nd, st = np.empty(n), np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int32)
-            try:
-                self.closest_vector(t, max_nodes, r2, z, v, cp, d2, nd, st, f)
-            except LgsError as e:
-                if e.code == LGS_ERR_OVERFLOW and not z64:
-                    continue
-                raise
-            return {"z": None if z is None else z.astype(np.int64, copy=False), "v": v, "cprime": cp,
-                    "dist2": d2, "nodes": nd, "status": st}
-        raise AssertionError("unreachable")
+            self.closest_vector(t, max_nodes, r2, z, v, cp, d2, nd, st, f)
+            return {"z": _z64(z), "v": v, "cprime": cp, "dist2": d2, "nodes": nd, "status": st}
+        return _host_retry(flags, call)
 
     # ---------------------------------------------------------------- diagnostics
     def series_stats(self, x, n_series, n, group_size, group_stride, series_stride, time_stride,

@@ -144,6 +144,11 @@ def test_writers_of_the_store_drop_the_key():
     assert "qkey_drop(c->bset[c->spec.j].qkey)" in fn("int spec_discard(lgs_ctx* c")
     sb = fn("int lgs_set_basis(lgs_ctx* c")
     assert "c->basis_gen += 1" in sb and "qkey_drop(s.qkey)" in sb
-    for name in ("int lgs_lattice_points(", "int lgs_log_density(", "int lgs_klein_targets(", "int lgs_klein_decode("):
+    for name in ("int lgs_lattice_points(", "int lgs_log_density("):
         assert "qkey_drop(c->qkey)" in fn(name), name
+    # the per-target entry points that write c->Z take it through the shared frame, which drops the key
+    take = src[src.index("    void* take_store() {"):]
+    assert "qkey_drop(c->qkey)" in take[:take.index("\n    }\n")]
+    for name in ("int run_decode(", "int lgs_klein_targets(", "int lgs_klein_decode(", "int lgs_imhk_targets("):
+        assert "t.take_store()" in fn(name) and "c->Z.p" not in fn(name), name
     assert "std::swap(c->qkey, s.qkey)" in src and "swap_buf(c->QCL, s.QCL)" in src
