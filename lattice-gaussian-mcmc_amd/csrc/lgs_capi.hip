@@ -16,6 +16,7 @@
 
 #include "../../include/lgs.h"
 #include "lgs_kernels.h"
+#include "lgs_mass_host.h"
 #include "lgs_qclean_host.h"
 #include "lgs_szc_host.h"
 
@@ -222,6 +223,10 @@ struct lgs_ctx {
     // the hand-out / live counters, the compaction map, the chunk's radius2 (host pointers)
     // and its per-target distance, node count and status (its returned points: DEC_Z)
     DevBuf CVP_ST[2], CVP_CTL, CVP_MAP, CVP_RAD, CVP_D2, CVP_NODES, CVP_STATUS;
+    // lgs_gaussian_mass (its state blocks, counters, map and radius2: the CVP_ buffers): the
+    // chunk's shift (host pointers), its work items (target | P[top], then the prefixes) and
+    // the items' results
+    DevBuf MASS_SHIFT, MASS_ITEMS, MASS_ITZ, MASS_OUT;
     bool has_q = false, has_binv = false;
     std::vector<Timer> pending;
     std::vector<hipEvent_t> pool;
@@ -1086,6 +1091,58 @@ struct TargetCall {
         return LGS_OK;
     }
 };
+
+// The launch loop of the enumerations (lgs_closest_vector: m targets; lgs_gaussian_mass: m
+// work items), over the state blocks 0 and 1 of S slots, all idle on entry, ctl zeroed.
+// launch(cur, live) advances slots [0, live) of block cur by at most `slice` nodes each
+// (timer 9); the host reads the two counters of ctl -- the next item to hand out, the slots
+// still working -- and relaunches.  Once no item waits and at most half the slots still work
+// (and more than a wave of them), the live slots, read from ids[cur] (>= 0: working), are
+// compacted into the other block by compact(cur, map, nlive) (timer 8).  While an item waits
+// every lane uses its whole slice, so at most m max_nodes / (live slice) launches end with
+// one waiting; after that every search is resumed at most ceil(max_nodes / slice) times, and
+// one launch hands out: beyond that bound the loop fails loudly.
+template <typename Launch, typename Compact>
+int run_enum_loop(lgs_ctx* c, const char* fn, int64_t m, int64_t S, int64_t max_nodes, int64_t slice,
+                  unsigned long long* ctl, int32_t* const ids[2], Launch launch, Compact compact) {
+    if (m <= 0) return LGS_OK;
+    int cur = 0;
+    int64_t live = std::min<int64_t>(S, m);
+    const double bound = std::ceil((double)m * (double)max_nodes / ((double)live * (double)slice)) +
+                         std::ceil((double)max_nodes / (double)slice) + 2.0;
+    std::vector<int32_t> ids_h, map_h;
+    for (double launches = 0.0;; launches += 1.0) {
+        if (launches > bound) return fail(LGS_ERR_HIP, "%s: launch bound exceeded (a library bug)", fn);
+        HIP_TRY(hipMemsetAsync(ctl + 1, 0, 8, c->stream));
+        {
+            Scope s(c, 9);
+            HIP_TRY(launch(cur, live));
+        }
+        unsigned long long cv[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(cv, ctl, 16, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        const int64_t nact = (int64_t)cv[1];
+        if (cv[0] < (unsigned long long)m) continue;  // items still wait for a slot
+        if (nact == 0) break;
+        if (nact * 2 <= live && live > 64) {  // compact the unfinished searches
+            ids_h.resize((size_t)live);
+            HIP_TRY(hipMemcpy(ids_h.data(), ids[cur], (size_t)live * 4, hipMemcpyDeviceToHost));
+            map_h.clear();
+            for (int64_t s = 0; s < live; ++s)
+                if (ids_h[(size_t)s] >= 0) map_h.push_back((int32_t)s);
+            if ((int64_t)map_h.size() != nact) return fail(LGS_ERR_HIP, "%s: live count mismatch (a library bug)", fn);
+            HIP_TRY(hipMemcpyAsync(c->CVP_MAP.p, map_h.data(), (size_t)nact * 4, hipMemcpyHostToDevice, c->stream));
+            {
+                Scope s(c, 8);
+                HIP_TRY(compact(cur, c->CVP_MAP.as<int32_t>(), nact));
+            }
+            HIP_TRY(hipStreamSynchronize(c->stream));  // (map_h is pageable host memory)
+            cur ^= 1;
+            live = nact;
+        }
+    }
+    return LGS_OK;
+}
 
 }  // namespace
 
@@ -3090,7 +3147,6 @@ int lgs_closest_vector(lgs_ctx* c, int64_t n, const double* targets, const doubl
     const lgs::CvpState st[2] = {lgs::cvp_state_at(c->CVP_ST[0].p, (int)d, S),
                                  lgs::cvp_state_at(c->CVP_ST[1].p, (int)d, S)};
     double* X = c->CPT.as<double>();
-    std::vector<int32_t> tgt_h, map_h;
     for (int64_t off = 0; off < n; off += chunk) {
         const int64_t m = t.chunk_at(off, chunk);
         if ((rc = t.centres(X, ldw))) return rc;
@@ -3123,47 +3179,18 @@ int lgs_closest_vector(lgs_ctx* c, int64_t n, const double* targets, const doubl
         HIP_TRY(hipMemsetAsync(a.W, 0, (size_t)ldw * d * ob, c->stream));
         HIP_TRY(hipMemsetAsync(a.ctl, 0, 16, c->stream));
         HIP_TRY(hipMemsetAsync(st[0].tgt, 0xff, (size_t)S * 4, c->stream));  // every slot idle
-        int cur = 0;
-        int64_t live = std::min<int64_t>(S, m);
-        // Launches: while a target waits every lane uses its whole slice, so at most
-        // m max_nodes / (live slice) launches end with one waiting; after that every search
-        // is resumed at most ceil(max_nodes / slice) times, and one launch hands out.
-        const double bound = std::ceil((double)m * (double)max_nodes / ((double)live * (double)slice)) +
-                             std::ceil((double)max_nodes / (double)slice) + 2.0;
-        for (double launches = 0.0;; launches += 1.0) {
-            if (launches > bound) return fail(LGS_ERR_HIP, "lgs_closest_vector: launch bound exceeded (a library bug)");
-            a.st = st[cur];
-            a.nslots = live;
-            HIP_TRY(hipMemsetAsync(a.ctl + 1, 0, 8, c->stream));
-            {
-                Scope s(c, 9);
-                HIP_TRY(lgs::launch::cvp_enum(a, ob, c->stream));
-            }
-            unsigned long long ctl[2] = {0, 0};
-            HIP_TRY(hipMemcpyAsync(ctl, a.ctl, 16, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            const int64_t nact = (int64_t)ctl[1];
-            if (ctl[0] < (unsigned long long)m) continue;  // targets still wait for a slot
-            if (nact == 0) break;
-            if (nact * 2 <= live && live > 64) {  // compact the unfinished searches
-                tgt_h.resize((size_t)live);
-                HIP_TRY(hipMemcpy(tgt_h.data(), st[cur].tgt, (size_t)live * 4, hipMemcpyDeviceToHost));
-                map_h.clear();
-                for (int64_t s = 0; s < live; ++s)
-                    if (tgt_h[(size_t)s] >= 0) map_h.push_back((int32_t)s);
-                if ((int64_t)map_h.size() != nact)
-                    return fail(LGS_ERR_HIP, "lgs_closest_vector: live count mismatch (a library bug)");
-                HIP_TRY(hipMemcpyAsync(c->CVP_MAP.p, map_h.data(), (size_t)nact * 4, hipMemcpyHostToDevice, c->stream));
-                {
-                    Scope s(c, 8);
-                    HIP_TRY(lgs::launch::cvp_compact(st[cur], st[cur ^ 1], S, c->CVP_MAP.as<int32_t>(), nact, (int)d,
-                                                     c->stream));
-                }
-                HIP_TRY(hipStreamSynchronize(c->stream));  // (map_h is pageable host memory)
-                cur ^= 1;
-                live = nact;
-            }
-        }
+        int32_t* const ids[2] = {st[0].tgt, st[1].tgt};
+        if ((rc = run_enum_loop(
+                 c, "lgs_closest_vector", m, S, max_nodes, slice, a.ctl, ids,
+                 [&](int cur, int64_t live) {
+                     a.st = st[cur];
+                     a.nslots = live;
+                     return lgs::launch::cvp_enum(a, ob, c->stream);
+                 },
+                 [&](int cur, const int32_t* map, int64_t nlive) {
+                     return lgs::launch::cvp_compact(st[cur], st[cur ^ 1], S, map, nlive, (int)d, c->stream);
+                 })))
+            return rc;
         void* Wp = a.W;
         c->hist.Z = nullptr;  // (no int16 history: B z reads the compact store)
         if ((rc = t.z_tail(Wp, ob, ldw)) || (rc = t.out_copy(o.dist2, a.dist2)) || (rc = t.out_copy(o.nodes, a.nodes)) ||
@@ -3172,6 +3199,205 @@ int lgs_closest_vector(lgs_ctx* c, int64_t n, const double* targets, const doubl
         if ((rc = finish(c))) return rc;
     }
     return finish(c);
+}
+
+// Exact Gaussian mass: lgs_closest_vector's search with a fixed radius and a weight on every
+// point (mass_enum_kernel, lgs_cvp.hip).  Per chunk of max_proposals targets:
+// the centres into CPT (timer 7) and, unless the call has 2^14 targets, back to the host,
+// which splits every tree into work items (lgs_mass_host.h); the enumeration of the items
+// (timer 9) with lgs_closest_vector's launch loop -- slices, hand-out of waiting items,
+// compaction (timer 8); the items' results to the host, summed per target, to the caller.
+int lgs_gaussian_mass(lgs_ctx* c, int64_t n, const double* targets, double sigma, const double* radius2,
+                      const double* shift, int64_t max_nodes, double* cprime_out, const lgs_mass_outputs* out,
+                      uint32_t flags) {
+    namespace mh = lgs::mass_host;
+    TargetCall t{c, n, targets, nullptr, nullptr, cprime_out};
+    int rc = t.open("lgs_gaussian_mass", flags, LGS_DEVICE_PTRS | LGS_COORD_MAJOR | LGS_TARGETS_QFRAME);
+    if (rc) return rc;
+    const lgs_mass_outputs none{};
+    const lgs_mass_outputs& o = out ? *out : none;
+    const bool moments = o.sum_z != nullptr;
+    if (c->d > LGS_MASS_MAX_D)
+        return fail(LGS_ERR_INVALID, "lgs_gaussian_mass: d = %lld > LGS_MASS_MAX_D (%d)", (long long)c->d,
+                    LGS_MASS_MAX_D);
+    if (moments && c->d > LGS_MASS_MOMENTS_MAX_D)
+        return fail(LGS_ERR_INVALID, "lgs_gaussian_mass: sum_z needs d <= LGS_MASS_MOMENTS_MAX_D (%d), d = %lld",
+                    LGS_MASS_MOMENTS_MAX_D, (long long)c->d);
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) return fail(LGS_ERR_INVALID, "sigma must be positive and finite");
+    const double two_s2 = 2.0 * sigma * sigma;
+    if (!(two_s2 > 0.0) || !std::isfinite(two_s2)) return fail(LGS_ERR_INVALID, "2 sigma^2 is not a positive fp64");
+    if (max_nodes < 1 || max_nodes > ((int64_t)1 << 40))
+        return fail(LGS_ERR_INVALID, "max_nodes must be 1..2^40");
+    if (n < 0) return fail(LGS_ERR_INVALID, "n < 0");
+    if (n == 0) return LGS_OK;
+    if ((rc = t.inputs())) return rc;
+    if (!radius2) return fail(LGS_ERR_INVALID, "null radius2: the ball of lgs_gaussian_mass is finite");
+    const bool dev = t.dev;
+    // radius2 and shift on the host: the checks are the host's, and so is the split
+    std::vector<double> rh, sh;
+    const double* r = radius2;
+    const double* sf = shift;
+    if (dev) {
+        rh.resize((size_t)n);
+        HIP_TRY(hipMemcpyAsync(rh.data(), radius2, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        if (shift) {
+            sh.resize((size_t)n);
+            HIP_TRY(hipMemcpyAsync(sh.data(), shift, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+            sf = sh.data();
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        r = rh.data();
+    }
+    for (int64_t k = 0; k < n; ++k) {
+        if (!(r[k] >= 0.0) || !std::isfinite(r[k]))
+            return fail(LGS_ERR_INVALID, "radius2[%lld] is negative or not finite", (long long)k);
+        if (sf && !std::isfinite(sf[k])) return fail(LGS_ERR_INVALID, "shift[%lld] is not finite", (long long)k);
+    }
+    const int64_t d = t.d;
+    int64_t slice = lgs::kCvpSlice, slots = lgs::kCvpMaxSlots;
+    int force_k = -1;
+    // (hooks build) lgs_closest_vector's LGS_TEST_CVP_SLICE / LGS_TEST_CVP_SLOTS, and
+    // LGS_TEST_MASS_SPLIT = k: the depth of the split, 0 = whole trees
+    if (const char* s = hook("LGS_TEST_CVP_SLICE")) slice = std::max<int64_t>(1, atoll(s));
+    if (const char* s = hook("LGS_TEST_CVP_SLOTS")) slots = std::max<int64_t>(1, atoll(s));
+    if (const char* s = hook("LGS_TEST_MASS_SPLIT"))
+        force_k = (int)std::min<int64_t>(std::max<int64_t>(0, atoll(s)), d - 1);
+    slots = (slots + 63) / 64 * 64;
+    const bool may_split = force_k > 0 || (force_k < 0 && n < mh::kItemsWanted && d > 1);
+    const int64_t chunk = std::min<int64_t>(n, c->max_props);
+    const int64_t ldw = (chunk + 63) / 64 * 64;
+    if ((rc = t.begin(chunk, ldw)) || (rc = c->CVP_CTL.reserve(16)) || (rc = c->CVP_MAP.reserve((size_t)slots * 4)) ||
+        (!dev && ((rc = c->CVP_RAD.reserve((size_t)chunk * 8)) ||
+                  (shift && (rc = c->MASS_SHIFT.reserve((size_t)chunk * 8))))))
+        return rc;
+    double* X = c->CPT.as<double>();
+    std::vector<double> Rh, cph, res;
+    if (may_split) {
+        Rh.resize((size_t)d * d);
+        HIP_TRY(hipMemcpyAsync(Rh.data(), c->R.p, (size_t)d * d * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    for (int64_t off = 0; off < n; off += chunk) {
+        const int64_t m = t.chunk_at(off, chunk);
+        if ((rc = t.centres(X, ldw))) return rc;
+        mh::Split sp;
+        if (may_split) {
+            cph.resize((size_t)d * ldw);
+            HIP_TRY(hipMemcpyAsync(cph.data(), X, (size_t)d * ldw * 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            sp = mh::split(Rh.data(), (int)d, m, n, cph.data(), ldw, r + off, force_k);
+            if (sp.nonfinite) {
+                if ((rc = finish(c))) return rc;
+                return fail(LGS_ERR_NONFINITE, "non-finite target or conditional mean");
+            }
+        } else {
+            sp = mh::split(nullptr, (int)d, m, n, nullptr, ldw, r + off, 0);
+        }
+        const int64_t items = sp.items;
+        const int64_t ldo = (std::max<int64_t>(items, 1) + 63) / 64 * 64;
+        const int64_t S = std::min<int64_t>(ldo, slots);
+        const size_t out_bytes = (size_t)ldo * (44 + (moments ? (size_t)d * 8 : 0));
+        if ((rc = c->CVP_ST[0].reserve(lgs::mass_state_bytes((int)d, S, moments))) ||
+            (rc = c->CVP_ST[1].reserve(lgs::mass_state_bytes((int)d, S, moments))) ||
+            (rc = c->MASS_OUT.reserve(out_bytes)) ||
+            (sp.k > 0 && ((rc = c->MASS_ITEMS.reserve((size_t)ldo * 12)) ||
+                          (rc = c->MASS_ITZ.reserve((size_t)ldo * sp.k * 8)))))
+            return rc;
+        const lgs::MassState st[2] = {lgs::mass_state_at(c->CVP_ST[0].p, (int)d, S, moments),
+                                      lgs::mass_state_at(c->CVP_ST[1].p, (int)d, S, moments)};
+        lgs::MassArgs a{};
+        a.d = (int)d;
+        a.top = sp.top;
+        a.m = items;
+        a.S = S;
+        a.max_nodes = max_nodes;
+        a.slice = slice;
+        a.two_s2 = two_s2;
+        a.R = c->R.as<double>();
+        a.CP = X;
+        a.ldc = ldw;
+        if (dev) {
+            a.radius2 = radius2 + off;
+            a.shift = shift ? shift + off : nullptr;
+        } else {
+            HIP_TRY(hipMemcpyAsync(c->CVP_RAD.p, radius2 + off, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+            a.radius2 = c->CVP_RAD.as<double>();
+            if (shift) {
+                HIP_TRY(hipMemcpyAsync(c->MASS_SHIFT.p, shift + off, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+                a.shift = c->MASS_SHIFT.as<double>();
+            }
+        }
+        if (sp.k > 0 && items > 0) {  // (sp outlives the copies: the launch loop synchronises)
+            double* itP = c->MASS_ITEMS.as<double>();
+            int32_t* itT = (int32_t*)(itP + ldo);
+            HIP_TRY(hipMemcpyAsync(itP, sp.P.data(), (size_t)items * 8, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(itT, sp.tgt.data(), (size_t)items * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->MASS_ITZ.p, sp.z.data(), (size_t)items * sp.k * 8, hipMemcpyHostToDevice,
+                                   c->stream));
+            a.it_P = itP;
+            a.it_tgt = itT;
+            a.it_z = c->MASS_ITZ.as<double>();
+            a.ldi = items;
+        }
+        a.ctl = c->CVP_CTL.as<unsigned long long>();
+        a.o_mass = c->MASS_OUT.as<double>();
+        a.o_energy = a.o_mass + ldo;
+        a.o_dmin = a.o_energy + ldo;
+        a.o_points = (int64_t*)(a.o_dmin + ldo);
+        a.o_nodes = a.o_points + ldo;
+        a.o_status = (int32_t*)(a.o_nodes + ldo);
+        a.o_sz = moments ? (double*)((char*)c->MASS_OUT.p + (size_t)ldo * 44) : nullptr;
+        a.ldo = ldo;
+        a.flags = c->flags.as<unsigned int>();
+        HIP_TRY(hipMemsetAsync(a.ctl, 0, 16, c->stream));
+        HIP_TRY(hipMemsetAsync(st[0].item, 0xff, (size_t)S * 4, c->stream));  // every slot idle
+        int32_t* const ids[2] = {st[0].item, st[1].item};
+        if ((rc = run_enum_loop(
+                 c, "lgs_gaussian_mass", items, S, max_nodes, slice, a.ctl, ids,
+                 [&](int cur, int64_t live) {
+                     a.st = st[cur];
+                     a.nslots = live;
+                     return lgs::launch::mass_enum(a, moments, c->stream);
+                 },
+                 [&](int cur, const int32_t* map, int64_t nlive) {
+                     return lgs::launch::mass_compact(st[cur], st[cur ^ 1], S, map, nlive, (int)d, moments, c->stream);
+                 })))
+            return rc;
+        if ((rc = t.cprime_tail(X, ldw))) return rc;
+        res.assign(out_bytes / 8, 0.0);
+        if (items > 0)
+            HIP_TRY(hipMemcpyAsync(res.data(), c->MASS_OUT.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = finish(c))) return rc;  // (synchronises; a lane's non-finite mean is reported here)
+        mh::ItemResults ir{};
+        ir.mass = res.data();
+        ir.energy = ir.mass + ldo;
+        ir.dmin = ir.energy + ldo;
+        ir.points = (const int64_t*)(ir.dmin + ldo);
+        ir.nodes = ir.points + ldo;
+        ir.status = (const int32_t*)(ir.nodes + ldo);
+        ir.sz = moments ? (const double*)((const char*)res.data() + (size_t)ldo * 44) : nullptr;
+        ir.ldo = ldo;
+        std::vector<double> tm((size_t)m), te((size_t)m), td((size_t)m), tz(moments ? (size_t)m * d : 0);
+        std::vector<int64_t> tp((size_t)m), tn((size_t)m);
+        std::vector<int32_t> ts((size_t)m);
+        mh::combine(sp, max_nodes, ir,
+                    mh::TargetResults{tm.data(), te.data(), td.data(), moments ? tz.data() : nullptr, tp.data(),
+                                      tn.data(), ts.data()});
+        // (the sums are the host's: to the caller's arrays, device or host)
+        auto put = [&](void* user, const void* src, size_t bytes) {
+            if (!user) return hipSuccess;
+            if (dev) return hipMemcpy(user, src, bytes, hipMemcpyHostToDevice);
+            memcpy(user, src, bytes);
+            return hipSuccess;
+        };
+        HIP_TRY(put(o.mass ? o.mass + off : nullptr, tm.data(), (size_t)m * 8));
+        HIP_TRY(put(o.energy ? o.energy + off : nullptr, te.data(), (size_t)m * 8));
+        HIP_TRY(put(o.dist2_min ? o.dist2_min + off : nullptr, td.data(), (size_t)m * 8));
+        HIP_TRY(put(o.points ? o.points + off : nullptr, tp.data(), (size_t)m * 8));
+        HIP_TRY(put(o.nodes ? o.nodes + off : nullptr, tn.data(), (size_t)m * 8));
+        HIP_TRY(put(o.status ? o.status + off : nullptr, ts.data(), (size_t)m * 4));
+        HIP_TRY(put(o.sum_z ? o.sum_z + (size_t)off * d : nullptr, tz.data(), (size_t)m * d * 8));
+    }
+    return LGS_OK;
 }
 
 }  // extern "C"

@@ -299,6 +299,83 @@ struct CvpArgs {
     unsigned int* flags;  // the context's flag words (kFlagNonFinite, kFlagOverflow)
 };
 
+// ---- exact Gaussian mass: fixed-radius enumeration (lgs_cvp.hip, lgs_gaussian_mass)
+// The search of lgs_cvp.hip with a bound that never shrinks and a weight on every leaf.  A
+// work item is a partial tree: (target, top, prefix) -- the lane starts on level top - 1
+// below the node z[top .. d-1] with partial distance P[top], and stops when it climbs back
+// to `top` (top = d: the whole tree, no prefix).  kCvpSlice, kCvpMaxSlots, kCvpLanes and
+// kCvpMaxAbsZ hold here too.
+constexpr int kMassMaxD = kCvpMaxD;     // LGS_MASS_MAX_D
+constexpr int kMassMomentsMaxD = 40;    // LGS_MASS_MOMENTS_MAX_D: msub | S join base | P | z | sn in LDS
+// LDS of a block: R, then base | P | z | sn (| msub | S with moments) of its lanes
+inline size_t mass_lds_bytes(int d, bool moments) {
+    return ((size_t)d * d + (size_t)(moments ? 6 : 4) * d * kCvpLanes) * 8;
+}
+// The state of one slot, CvpState's layout rules: element (i, s) at [i * S + s].
+struct MassState {
+    double* z;       // d x S
+    double* base;    // d x S
+    double* P;       // d x S (P[top] is the item's, levels above it unused)
+    double* sn;      // d x S
+    double* msub;    // d x S (moments): the weight below the current node of level i, 1 <= i < top
+    double* Sz;      // d x S (moments): sum of weight * z_i over the subtrees left so far, i < top
+    double* mass;    // S
+    double* energy;  // S
+    double* dmin;    // S
+    int64_t* points; // S
+    int64_t* nodes;  // S
+    int32_t* item;   // S: the work item the slot is on, -1 = idle
+    int32_t* lvl;    // S
+};
+inline size_t mass_state_bytes(int d, int64_t S, bool moments) {
+    return (size_t)S * ((size_t)d * (moments ? 48 : 32) + 48);
+}
+inline MassState mass_state_at(void* p, int d, int64_t S, bool moments) {  // (S a multiple of 64)
+    MassState s;
+    const size_t n = (size_t)d * S;
+    s.z = (double*)p;
+    s.base = s.z + n;
+    s.P = s.base + n;
+    s.sn = s.P + n;
+    s.msub = s.sn + n;
+    s.Sz = s.msub + (moments ? n : 0);
+    s.mass = s.Sz + (moments ? n : 0);
+    s.energy = s.mass + S;
+    s.dmin = s.energy + S;
+    s.points = (int64_t*)(s.dmin + S);
+    s.nodes = s.points + S;
+    s.item = (int32_t*)(s.nodes + S);
+    s.lvl = s.item + S;
+    return s;
+}
+struct MassArgs {
+    int d;
+    int top;             // the level the items hang from (d: whole trees)
+    int64_t m;           // work items of the chunk
+    int64_t nslots;      // lanes of this launch
+    int64_t S;           // the state block's slot count
+    int64_t max_nodes;   // per item
+    int64_t slice;       // per lane and launch
+    double two_s2;       // 2 sigma^2
+    const double* R;     // row-major d x d
+    const double* CP;    // the targets' centres, coordinate-major: CP[i * ldc + t]
+    int64_t ldc;
+    const double* radius2;  // per target
+    const double* shift;    // per target, nullable (0)
+    const int32_t* it_tgt;  // m: the item's target (nullptr: item q is target q)
+    const double* it_z;     // (d - top) x ldi: z[top + r] of item q at [r * ldi + q]
+    const double* it_P;     // m: P[top] (nullptr with top = d)
+    int64_t ldi;
+    MassState st;
+    unsigned long long* ctl;  // as CvpArgs::ctl
+    // per item: results (o_sz: d x ldo coordinate-major, rows top .. d-1 zero; moments only)
+    double *o_mass, *o_energy, *o_dmin, *o_sz;
+    int64_t *o_points, *o_nodes;
+    int32_t* o_status;   // 0 = the item's tree is done, 1 = max_nodes reached, 2 = a non-finite mean
+    int64_t ldo;
+    unsigned int* flags;
+};
+
 struct AcceptArgs {
     int64_t nc;
     int64_t T;
@@ -534,6 +611,13 @@ hipError_t cvp_enum(const CvpArgs& a, int zb, hipStream_t st);
 // Slots map[0 .. nlive) of src into slots 0 .. nlive - 1 of dst (blocks of S slots each)
 hipError_t cvp_compact(const CvpState& src, const CvpState& dst, int64_t S, const int32_t* map, int64_t nlive,
                        int d, hipStream_t st);
+// ---- exact Gaussian mass (lgs_cvp.hip)
+// One launch of the fixed-radius enumeration, as cvp_enum: every slot advances its work item
+// by at most a.slice nodes and takes the next waiting item when it stops.  moments: the
+// sum_z accumulators (d <= kMassMomentsMaxD).
+hipError_t mass_enum(const MassArgs& a, bool moments, hipStream_t st);
+hipError_t mass_compact(const MassState& src, const MassState& dst, int64_t S, const int32_t* map, int64_t nlive,
+                        int d, bool moments, hipStream_t st);
 hipError_t round_coeffs(const double* W, int64_t ldw, int d, int64_t n, int zb, void* Z, int64_t ldz,
                         unsigned int* flags, hipStream_t st);
 hipError_t check_range16(const void* zs, int ob, int64_t count, unsigned int* flags, hipStream_t st);

@@ -56,6 +56,8 @@ KERNEL_CPRIME = 7  # lgs_klein_targets: the c' = Q^T t stage (transposes + GEMM)
 KERNEL_DECODE_SELECT = 8  # lgs_klein_decode: the select and gather launches; lgs_imhk_targets: scan and gather
 KERNEL_CVP_ENUM = 9  # lgs_closest_vector: the enumeration launches
 LGS_CVP_MAX_D = 64
+LGS_MASS_MAX_D = 64          # lgs_gaussian_mass
+LGS_MASS_MOMENTS_MAX_D = 40  # ... with sum_z
 LGS_COUNTER_RESOLVED = 0
 LGS_COUNTER_FALLBACK = 1
 LGS_COUNTER_ACCEPT_RESOLVED = 2
@@ -75,7 +77,7 @@ EXPORTS = ("lgs_version", "lgs_last_error", "lgs_create", "lgs_create_ex", "lgs_
            "lgs_timing_get", "lgs_device_info", "lgs_series_stats", "lgs_gram",
            "lgs_jump_distance", "lgs_marginal_tvd", "lgs_column_range", "lgs_histogram", "lgs_set_decoder", "lgs_nearest_plane",
            "lgs_round_decode", "lgs_counter", "lgs_qskip_elided", "lgs_klein_targets", "lgs_klein_decode",
-           "lgs_imhk_targets", "lgs_closest_vector")
+           "lgs_imhk_targets", "lgs_closest_vector", "lgs_gaussian_mass")
 
 
 class ImhkOutputs(ctypes.Structure):
@@ -102,6 +104,13 @@ class ImhkTargetsOutputs(ctypes.Structure):
 class CvpOutputs(ctypes.Structure):
     """struct lgs_cvp_outputs (include/lgs.h)."""
     _fields_ = [("dist2", ctypes.c_void_p), ("nodes", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
+class MassOutputs(ctypes.Structure):
+    """struct lgs_mass_outputs (include/lgs.h)."""
+    _fields_ = [("mass", ctypes.c_void_p), ("energy", ctypes.c_void_p), ("points", ctypes.c_void_p),
+                ("dist2_min", ctypes.c_void_p), ("sum_z", ctypes.c_void_p), ("nodes", ctypes.c_void_p),
+                ("status", ctypes.c_void_p)]
 
 
 class LgsError(RuntimeError):
@@ -189,6 +198,9 @@ def load_library(path: str = LIB_PATH):
     if hasattr(L, "lgs_closest_vector"):  # (older A/B baselines lack it)
         L.lgs_closest_vector.argtypes = [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, ctypes.POINTER(CvpOutputs),
                                          ctypes.c_uint32]
+    if hasattr(L, "lgs_gaussian_mass"):  # (older A/B baselines lack it)
+        L.lgs_gaussian_mass.argtypes = [_vp, _i64, _vp, ctypes.c_double, _vp, _vp, _i64, _vp,
+                                        ctypes.POINTER(MassOutputs), ctypes.c_uint32]
     for name in EXPORTS:
         if name not in ("lgs_version", "lgs_last_error") and hasattr(L, name):
             getattr(L, name).restype = ctypes.c_int
@@ -676,6 +688,80 @@ class Context:
             self.closest_vector(t, max_nodes, r2, z, v, cp, d2, nd, st, f)
             return {"z": _z64(z), "v": v, "cprime": cp, "dist2": d2, "nodes": nd, "status": st}
         return _host_retry(flags, call)
+
+    # ---------------------------------------------------------------- exact Gaussian mass
+    _MASS_FLAGS = LGS_DEVICE_PTRS | LGS_COORD_MAJOR | LGS_TARGETS_QFRAME
+
+    def _mass_args(self, targets, sigma, max_nodes, flags, moments):
+        """Argument checks of gaussian_mass / gaussian_mass_host, before any library call."""
+        if isinstance(flags, bool) or not isinstance(flags, (int, np.integer)) or flags & ~self._MASS_FLAGS:
+            raise ValueError(f"gaussian_mass: unsupported flags {flags!r}")
+        if self.d > LGS_MASS_MAX_D:
+            raise ValueError(f"gaussian_mass supports d <= {LGS_MASS_MAX_D}, the loaded basis has d = {self.d}")
+        if moments and self.d > LGS_MASS_MOMENTS_MAX_D:
+            raise ValueError(f"gaussian_mass: sum_z supports d <= {LGS_MASS_MOMENTS_MAX_D}, "
+                             f"the loaded basis has d = {self.d}")
+        if isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.integer, np.floating)) or \
+                not (sigma > 0 and np.isfinite(sigma)):
+            raise ValueError(f"sigma must be a positive finite number, got {sigma!r}")
+        if isinstance(max_nodes, bool) or not isinstance(max_nodes, (int, np.integer)) or \
+                not 1 <= max_nodes <= 1 << 40:
+            raise ValueError(f"max_nodes must be an integer in 1..2^40, got {max_nodes!r}")
+        return self._n_targets(targets, flags)
+
+    def gaussian_mass(self, targets, sigma, radius2, shift=None, max_nodes=1 << 26, cprime_out=None, mass=None,
+                      energy=None, points=None, dist2_min=None, sum_z=None, nodes=None, status=None, flags=0):
+        """Raw lgs_gaussian_mass on caller buffers (numpy host or device tensors): the Gaussian
+        weight, at width sigma, of the lattice points with squared distance below radius2 of
+        each target, by fixed-radius enumeration.  targets as in closest_vector; radius2 (n,)
+        float64, required; shift (n,) float64 (subtracted from the squared distance inside the
+        exponential); mass / energy / dist2_min (n,) float64, points / nodes (n,) int64, status
+        (n,) int32, sum_z (n, d) float64, all optional."""
+        n = self._mass_args(targets, sigma, max_nodes, flags, sum_z is not None)
+        if radius2 is None:
+            raise ValueError("radius2 is required: the ball of gaussian_mass is finite")
+        _check_bufs(flags, self.device, ((targets, "float64", "targets"), (radius2, "float64", "radius2"),
+                                         (shift, "float64", "shift"), (cprime_out, "float64", "cprime_out"),
+                                         (mass, "float64", "mass"), (energy, "float64", "energy"),
+                                         (points, "int64", "points"), (dist2_min, "float64", "dist2_min"),
+                                         (sum_z, "float64", "sum_z"), (nodes, "int64", "nodes"),
+                                         (status, "int32", "status")))
+        for a, want, name in ((cprime_out, (n, self.d), "cprime_out"), (radius2, (n,), "radius2"),
+                              (shift, (n,), "shift"), (mass, (n,), "mass"), (energy, (n,), "energy"),
+                              (points, (n,), "points"), (dist2_min, (n,), "dist2_min"), (sum_z, (n, self.d), "sum_z"),
+                              (nodes, (n,), "nodes"), (status, (n,), "status")):
+            if a is not None and not isinstance(a, int) and tuple(a.shape) != want:
+                raise ValueError(f"{name}: expected shape {want}, got {tuple(a.shape)}")
+        self._ck(self._L.lgs_gaussian_mass(self._h, n, _ptr(targets), float(sigma), _ptr(radius2), _ptr(shift),
+                                           int(max_nodes), _ptr(cprime_out),
+                                           _outputs(MassOutputs, mass, energy, points, dist2_min, sum_z, nodes,
+                                                    status), int(flags)))
+
+    def gaussian_mass_host(self, targets, sigma, radius2, shift=None, max_nodes=1 << 26, *, moments=False,
+                           want_cprime=False, flags=0):
+        """lgs_gaussian_mass of host targets (n, d) into fresh host arrays {"mass", "energy",
+        "points", "dist2_min", "sum_z" (None without moments), "nodes", "status", "cprime"}."""
+        if isinstance(flags, (int, np.integer)) and flags & (LGS_DEVICE_PTRS | LGS_COORD_MAJOR):
+            raise ValueError("gaussian_mass_host takes row-major host targets")
+        t = np.ascontiguousarray(targets, dtype=np.float64)
+        n = self._mass_args(t, sigma, max_nodes, flags, moments)
+        if radius2 is None:
+            raise ValueError("radius2 is required: the ball of gaussian_mass is finite")
+        r2 = np.ascontiguousarray(radius2, dtype=np.float64)
+        if r2.shape != (n,) or not np.all((r2 >= 0) & np.isfinite(r2)):
+            raise ValueError(f"radius2 must hold {n} finite non-negative values")
+        sh = None
+        if shift is not None:
+            sh = np.ascontiguousarray(shift, dtype=np.float64)
+            if sh.shape != (n,) or not np.all(np.isfinite(sh)):
+                raise ValueError(f"shift must hold {n} finite values")
+        r = {"mass": np.empty(n), "energy": np.empty(n), "points": np.empty(n, dtype=np.int64),
+             "dist2_min": np.empty(n), "sum_z": np.empty((n, self.d)) if moments else None,
+             "nodes": np.empty(n, dtype=np.int64), "status": np.empty(n, dtype=np.int32),
+             "cprime": np.empty((n, self.d)) if want_cprime else None}
+        self.gaussian_mass(t, sigma, r2, sh, max_nodes, r["cprime"], r["mass"], r["energy"], r["points"],
+                           r["dist2_min"], r["sum_z"], r["nodes"], r["status"], flags)
+        return r
 
     # ---------------------------------------------------------------- diagnostics
     def series_stats(self, x, n_series, n, group_size, group_stride, series_stride, time_stride,

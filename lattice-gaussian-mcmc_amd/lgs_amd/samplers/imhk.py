@@ -294,12 +294,22 @@ class IMHKSampler(DiscreteGaussianSampler):
             self._lnmax = float(np.sum(ln))
         return self._lnmax
 
-    def compute_delta(self, num_samples: int = 1 << 16) -> float:
+    def compute_delta(self, num_samples: int = 1 << 16, *, exact: bool = False, nats: float = 40.0,
+                      max_nodes: int = 1 << 26) -> float:
         """Monte Carlo estimate of Wang & Ling's delta = rho_{sigma,c}(L) / prod_i rho_{sigma_i}(Z)
         (the quantity of imhk.py:256-258 and the aspirational IndependentMHK.compute_delta of
         experiments/cryptographic_experiments.py:288): rho(L) = E_Klein[w(x)] with the exact
         weight w(x) = prod_i rho_{sigma_i}(Z - mu_i(x)), drawn on the GPU
-        (lgs_klein with LGS_WANG_LING log-weights)."""
+        (lgs_klein with LGS_WANG_LING log-weights).
+
+        ``exact=True``: rho_{sigma,c}(L) by enumeration instead (``lgs_gaussian_mass`` over
+        the points within 2 sigma^2 ``nats`` of the closest one's squared distance, d <= 64):
+        a lower bound of delta that loses only the truncated tail, with no sampling error.
+        Raises RuntimeError when the ball holds more than ``max_nodes`` tree nodes -- possibly
+        only after a multiple of that work (``Decoder.gaussian_mass``): at d beyond a dozen
+        or so pass a smaller ``nats``."""
+        if exact:
+            return float(np.exp(self._exact_log_mass(nats, max_nodes) - self._log_normaliser_max()))
         r = self.proposal_sampler._draw(int(num_samples), want_v=False, want_logw=True,
                                         flags=_capi.LGS_WANG_LING)
         lw = r["logw"]
@@ -307,13 +317,27 @@ class IMHKSampler(DiscreteGaussianSampler):
         log_mean = m + float(np.log(np.mean(np.exp(lw - m))))
         return float(np.exp(log_mean - self._log_normaliser_max()))
 
-    def spectral_gap(self, num_samples: int = 1 << 16) -> float:
-        """Spectral gap of the IMHK kernel: delta (uniform ergodicity, ||P^t - pi|| <= (1-delta)^t)."""
-        return self.compute_delta(num_samples)
+    def _exact_log_mass(self, nats: float, max_nodes: int) -> float:
+        """log rho_{sigma,c}(L) over the truncated ball, by enumeration around the sampler's own
+        c' on its own context (neither call reads the loaded sigma or centre)."""
+        from ..decode import gaussian_mass_around
+        if self.dimension > _capi.LGS_MASS_MAX_D:
+            raise ValueError(f"exact delta supports d <= {_capi.LGS_MASS_MAX_D}, got {self.dimension}")
+        cp = np.asarray(self.proposal_sampler.center_transformed, dtype=np.float64).reshape(1, self.dimension)
+        r = gaussian_mass_around(self.context, cp, float(self.sigma), nats, max_nodes,
+                                 flags=_capi.LGS_TARGETS_QFRAME)
+        if int(r["status"][0]) != 0:
+            raise RuntimeError(f"exact delta: the ball of {nats} nats holds more than {int(max_nodes)} tree nodes: "
+                               f"raise max_nodes or lower nats")
+        return float(r["log_mass"][0])
 
-    def mixing_time(self, epsilon: float = 0.25, num_samples: int = 1 << 16) -> int:
+    def spectral_gap(self, num_samples: int = 1 << 16, *, exact: bool = False, **kw) -> float:
+        """Spectral gap of the IMHK kernel: delta (uniform ergodicity, ||P^t - pi|| <= (1-delta)^t)."""
+        return self.compute_delta(num_samples, exact=exact, **kw)
+
+    def mixing_time(self, epsilon: float = 0.25, num_samples: int = 1 << 16, *, exact: bool = False, **kw) -> int:
         """t_mix(epsilon) <= ceil(ln(epsilon) / ln(1 - delta))."""
-        delta = self.compute_delta(num_samples)
+        delta = self.compute_delta(num_samples, exact=exact, **kw)
         if delta >= 1.0:
             return 1
         if delta <= 0.0:
