@@ -227,6 +227,15 @@ struct lgs_ctx {
     // chunk's shift (host pointers), its work items (target | P[top], then the prefixes) and
     // the items' results
     DevBuf MASS_SHIFT, MASS_ITEMS, MASS_ITZ, MASS_OUT;
+    // lgs_ball_points with host pointers: the listed rows (z | D) before they go to the caller
+    DevBuf BALL_Z, BALL_D;
+    // lgs_exact_table: the table lgs_exact_sample draws from -- the rows (z of tbl_zb bytes, D),
+    // their weights and running sums, the targets' row and block offsets, the block totals and
+    // prefixes, the masses (lgs_set_basis discards it)
+    DevBuf TBL_Z, TBL_D, TBL_W, TBL_S, TBL_OFF, TBL_BOFF, TBL_BTOT, TBL_BPRE, TBL_M;
+    bool has_table = false;
+    int64_t tbl_n = 0, tbl_rows = 0;
+    int tbl_zb = 4;
     bool has_q = false, has_binv = false;
     std::vector<Timer> pending;
     std::vector<hipEvent_t> pool;
@@ -1144,6 +1153,287 @@ int run_enum_loop(lgs_ctx* c, const char* fn, int64_t m, int64_t S, int64_t max_
     return LGS_OK;
 }
 
+// radius2 (required) and shift (nullable) of a fixed-radius call on the host, checked: the
+// checks are the host's, and so is the split.  r / sf: the host arrays (the caller's own, or
+// rh / sh filled from the device).
+int mass_radius_host(lgs_ctx* c, bool dev, int64_t n, const double* radius2, const double* shift,
+                     std::vector<double>& rh, std::vector<double>& sh, const double*& r, const double*& sf) {
+    r = radius2;
+    sf = shift;
+    if (dev) {
+        rh.resize((size_t)n);
+        HIP_TRY(hipMemcpyAsync(rh.data(), radius2, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        if (shift) {
+            sh.resize((size_t)n);
+            HIP_TRY(hipMemcpyAsync(sh.data(), shift, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+            sf = sh.data();
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        r = rh.data();
+    }
+    for (int64_t k = 0; k < n; ++k) {
+        if (!(r[k] >= 0.0) || !std::isfinite(r[k]))
+            return fail(LGS_ERR_INVALID, "radius2[%lld] is negative or not finite", (long long)k);
+        if (sf && !std::isfinite(sf[k])) return fail(LGS_ERR_INVALID, "shift[%lld] is not finite", (long long)k);
+    }
+    return LGS_OK;
+}
+
+// The two passes of lgs_ball_points and lgs_exact_table over the machinery of
+// lgs_gaussian_mass.  The counting pass is that call's own -- per chunk the centres (timer 7),
+// the host's split into work items, mass_enum_kernel (timer 9, compaction 8), the items'
+// counts summed per target -- and yields offsets, nodes and status.  The items are emitted
+// in traversal order, so an exclusive prefix of their point counts, in item order, gives
+// every item its first row; the listing pass runs the same items of the complete targets
+// again (those with a point) and writes row first + (points of the item so far).
+struct BallCall {
+    const double* radius2 = nullptr;  // the caller's (a device array with LGS_DEVICE_PTRS)
+    const double* r = nullptr;        // the same on the host, checked
+    int64_t max_nodes = 0, capacity = 0;
+    int zb = 4;                       // element width of the rows
+    bool table = false;               // the rows go to the context's table (TBL_Z, TBL_D) and are
+                                      // wanted only if every target is complete and has a point
+    void* z_dst = nullptr;            // else: the caller's z_out / dist2_out
+    double* d_dst = nullptr;
+    std::vector<int64_t> offsets, nodes;  // n + 1, n
+    std::vector<int32_t> status;          // n
+    bool listed = false;                  // the rows were written
+    int64_t bad_status = -1, bad_empty = -1;  // the first target over its budget / without a point
+};
+
+int ball_run(lgs_ctx* c, const char* fn, TargetCall& t, BallCall& b) {
+    namespace mh = lgs::mass_host;
+    const int64_t n = t.n, d = t.d;
+    const bool dev = t.dev;
+    int rc;
+    int64_t slice = lgs::kCvpSlice, slots = lgs::kCvpMaxSlots;
+    int force_k = -1;
+    // (hooks build) as lgs_gaussian_mass
+    if (const char* s = hook("LGS_TEST_CVP_SLICE")) slice = std::max<int64_t>(1, atoll(s));
+    if (const char* s = hook("LGS_TEST_CVP_SLOTS")) slots = std::max<int64_t>(1, atoll(s));
+    if (const char* s = hook("LGS_TEST_MASS_SPLIT"))
+        force_k = (int)std::min<int64_t>(std::max<int64_t>(0, atoll(s)), d - 1);
+    slots = (slots + 63) / 64 * 64;
+    const bool may_split = force_k > 0 || (force_k < 0 && n < mh::kItemsWanted && d > 1);
+    const int64_t chunk = std::min<int64_t>(n, c->max_props);
+    const int64_t ldw = (chunk + 63) / 64 * 64;
+    if ((rc = t.begin(chunk, ldw)) || (rc = c->CVP_CTL.reserve(16)) || (rc = c->CVP_MAP.reserve((size_t)slots * 4)) ||
+        (!dev && (rc = c->CVP_RAD.reserve((size_t)chunk * 8))))
+        return rc;
+    double* X = c->CPT.as<double>();
+    std::vector<double> Rh, cph, res;
+    if (may_split) {
+        Rh.resize((size_t)d * d);
+        HIP_TRY(hipMemcpyAsync(Rh.data(), c->R.p, (size_t)d * d * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    lgs::MassArgs a{};
+    a.d = (int)d;
+    a.max_nodes = b.max_nodes;
+    a.slice = slice;
+    a.two_s2 = INFINITY;  // (the counting pass's weights are exp(-0) = 1: its mass is not used)
+    a.R = c->R.as<double>();
+    a.CP = X;
+    a.ldc = ldw;
+    a.ctl = c->CVP_CTL.as<unsigned long long>();
+    a.flags = c->flags.as<unsigned int>();
+    // One pass over the items of a chunk (its targets off .. off + m - 1): first = nullptr,
+    // the counting pass; else the listing pass.  The host arrays outlive the copies: the
+    // launch loop synchronises.
+    auto run_items = [&](int64_t off, int64_t m, int top, int k, int64_t items, const int32_t* tgt, const double* P,
+                         const double* z, const int64_t* first) -> int {
+        int rc;
+        const int64_t ldo = (std::max<int64_t>(items, 1) + 63) / 64 * 64;
+        const int64_t S = std::min<int64_t>(ldo, slots);
+        if ((rc = c->CVP_ST[0].reserve(lgs::mass_state_bytes((int)d, S, false))) ||
+            (rc = c->CVP_ST[1].reserve(lgs::mass_state_bytes((int)d, S, false))) ||
+            (rc = c->MASS_OUT.reserve((size_t)ldo * 44)) || (rc = c->MASS_ITEMS.reserve((size_t)ldo * 20)) ||
+            (k > 0 && (rc = c->MASS_ITZ.reserve((size_t)ldo * k * 8))))
+            return rc;
+        const lgs::MassState st[2] = {lgs::mass_state_at(c->CVP_ST[0].p, (int)d, S, false),
+                                      lgs::mass_state_at(c->CVP_ST[1].p, (int)d, S, false)};
+        a.top = top;
+        a.m = items;
+        a.S = S;
+        if (dev) {
+            a.radius2 = b.radius2 + off;
+        } else {
+            HIP_TRY(hipMemcpyAsync(c->CVP_RAD.p, b.radius2 + off, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+            a.radius2 = c->CVP_RAD.as<double>();
+        }
+        a.it_P = nullptr;
+        a.it_tgt = nullptr;
+        a.it_z = nullptr;
+        a.it_first = nullptr;
+        a.ldi = 0;
+        if (items > 0 && (k > 0 || first)) {
+            double* itP = c->MASS_ITEMS.as<double>();
+            int64_t* itF = (int64_t*)(itP + ldo);
+            int32_t* itT = (int32_t*)(itF + ldo);
+            HIP_TRY(hipMemcpyAsync(itP, P, (size_t)items * 8, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(itT, tgt, (size_t)items * 4, hipMemcpyHostToDevice, c->stream));
+            a.it_P = itP;
+            a.it_tgt = itT;
+            if (k > 0) {
+                HIP_TRY(hipMemcpyAsync(c->MASS_ITZ.p, z, (size_t)items * k * 8, hipMemcpyHostToDevice, c->stream));
+                a.it_z = c->MASS_ITZ.as<double>();
+                a.ldi = items;
+            }
+            if (first) {
+                HIP_TRY(hipMemcpyAsync(itF, first, (size_t)items * 8, hipMemcpyHostToDevice, c->stream));
+                a.it_first = itF;
+            }
+        }
+        a.o_mass = c->MASS_OUT.as<double>();
+        a.o_energy = a.o_mass + ldo;
+        a.o_dmin = a.o_energy + ldo;
+        a.o_points = (int64_t*)(a.o_dmin + ldo);
+        a.o_nodes = a.o_points + ldo;
+        a.o_status = (int32_t*)(a.o_nodes + ldo);
+        a.o_sz = nullptr;
+        a.ldo = ldo;
+        HIP_TRY(hipMemsetAsync(a.ctl, 0, 16, c->stream));
+        HIP_TRY(hipMemsetAsync(st[0].item, 0xff, (size_t)S * 4, c->stream));  // every slot idle
+        int32_t* const ids[2] = {st[0].item, st[1].item};
+        return run_enum_loop(
+            c, fn, items, S, b.max_nodes, slice, a.ctl, ids,
+            [&](int cur, int64_t live) {
+                a.st = st[cur];
+                a.nslots = live;
+                return first ? lgs::launch::mass_list(a, c->stream) : lgs::launch::mass_enum(a, false, c->stream);
+            },
+            [&](int cur, const int32_t* map, int64_t nlive) {
+                return lgs::launch::mass_compact(st[cur], st[cur ^ 1], S, map, nlive, (int)d, false, c->stream);
+            });
+    };
+
+    struct Chunk {
+        mh::Split sp;
+        std::vector<int64_t> ipts;  // points per item
+    };
+    std::vector<Chunk> chunks;
+    std::vector<int64_t> tpts((size_t)n);
+    b.offsets.assign((size_t)n + 1, 0);
+    b.nodes.assign((size_t)n, 0);
+    b.status.assign((size_t)n, 0);
+    b.listed = false;
+    for (int64_t off = 0; off < n; off += chunk) {  // the counting pass
+        const int64_t m = t.chunk_at(off, chunk);
+        if ((rc = t.centres(X, ldw))) return rc;
+        chunks.emplace_back();
+        mh::Split& sp = chunks.back().sp;
+        if (may_split) {
+            cph.resize((size_t)d * ldw);
+            HIP_TRY(hipMemcpyAsync(cph.data(), X, (size_t)d * ldw * 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            sp = mh::split(Rh.data(), (int)d, m, n, cph.data(), ldw, b.r + off, force_k);
+            if (sp.nonfinite) {
+                if ((rc = finish(c))) return rc;
+                return fail(LGS_ERR_NONFINITE, "non-finite target or conditional mean");
+            }
+        } else {
+            sp = mh::split(nullptr, (int)d, m, n, nullptr, ldw, b.r + off, 0);
+        }
+        const int64_t items = sp.items;
+        const int64_t ldo = (std::max<int64_t>(items, 1) + 63) / 64 * 64;
+        if ((rc = run_items(off, m, sp.top, sp.k, items, sp.tgt.data(), sp.P.data(), sp.z.data(), nullptr))) return rc;
+        if ((rc = t.cprime_tail(X, ldw))) return rc;
+        res.assign((size_t)ldo * 44 / 8, 0.0);
+        if (items > 0)
+            HIP_TRY(hipMemcpyAsync(res.data(), c->MASS_OUT.p, (size_t)ldo * 44, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = finish(c))) return rc;  // (synchronises; a lane's non-finite mean is reported here)
+        mh::ItemResults ir{};
+        ir.mass = res.data();
+        ir.energy = ir.mass + ldo;
+        ir.dmin = ir.energy + ldo;
+        ir.points = (const int64_t*)(ir.dmin + ldo);
+        ir.nodes = ir.points + ldo;
+        ir.status = (const int32_t*)(ir.nodes + ldo);
+        ir.ldo = ldo;
+        std::vector<double> tm((size_t)m), te((size_t)m), td((size_t)m);
+        mh::combine(sp, b.max_nodes, ir,
+                    mh::TargetResults{tm.data(), te.data(), td.data(), nullptr, tpts.data() + off, b.nodes.data() + off,
+                                      b.status.data() + off});
+        chunks.back().ipts.assign(ir.points, ir.points + items);
+    }
+    b.bad_status = b.bad_empty = -1;
+    for (int64_t k = 0; k < n; ++k) {
+        const bool over = b.status[(size_t)k] != 0;
+        if (over && b.bad_status < 0) b.bad_status = k;
+        if (!over && tpts[(size_t)k] == 0 && b.bad_empty < 0) b.bad_empty = k;
+        b.offsets[(size_t)k + 1] = b.offsets[(size_t)k] + (over ? 0 : tpts[(size_t)k]);
+    }
+    const int64_t total = b.offsets[(size_t)n];
+    if (total > b.capacity || total == 0) return LGS_OK;
+    if (b.table && (b.bad_status >= 0 || b.bad_empty >= 0)) return LGS_OK;
+
+    void* zdev = b.z_dst;
+    double* ddev = b.d_dst;
+    if (b.table) {
+        if ((rc = c->TBL_Z.reserve((size_t)total * d * b.zb)) || (rc = c->TBL_D.reserve((size_t)total * 8))) return rc;
+        zdev = c->TBL_Z.p;
+        ddev = c->TBL_D.as<double>();
+    } else if (!dev) {
+        if ((rc = c->BALL_Z.reserve((size_t)total * d * b.zb)) || (rc = c->BALL_D.reserve((size_t)total * 8))) return rc;
+        zdev = c->BALL_Z.p;
+        ddev = c->BALL_D.as<double>();
+    }
+    a.l_z = zdev;
+    a.l_d = ddev;
+    a.l_zb = b.zb;
+    a.l_rows = total;
+    std::vector<int32_t> ftgt;
+    std::vector<double> fP, fz;
+    std::vector<int64_t> ffirst, fq, run;
+    size_t ci = 0;
+    for (int64_t off = 0; off < n; off += chunk, ++ci) {  // the listing pass
+        const int64_t m = t.chunk_at(off, chunk);
+        const mh::Split& sp = chunks[ci].sp;
+        const std::vector<int64_t>& ipts = chunks[ci].ipts;
+        ftgt.clear();
+        fP.clear();
+        ffirst.clear();
+        fq.clear();
+        run.assign((size_t)m, 0);
+        for (int64_t q = 0; q < sp.items; ++q) {
+            const int64_t tg = sp.tgt[(size_t)q];
+            if (b.status[(size_t)(off + tg)] != 0 || ipts[(size_t)q] == 0) continue;
+            ftgt.push_back((int32_t)tg);
+            fP.push_back(sp.P[(size_t)q]);
+            ffirst.push_back(b.offsets[(size_t)(off + tg)] + run[(size_t)tg]);
+            fq.push_back(q);
+            run[(size_t)tg] += ipts[(size_t)q];
+        }
+        const int64_t nf = (int64_t)fq.size();
+        if (nf == 0) continue;
+        fz.resize((size_t)nf * sp.k);
+        for (int r = 0; r < sp.k; ++r)
+            for (int64_t j = 0; j < nf; ++j) fz[(size_t)r * nf + j] = sp.z[(size_t)r * sp.items + fq[(size_t)j]];
+        if (chunks.size() > 1 && (rc = t.centres(X, ldw))) return rc;  // (one chunk: X still holds its centres)
+        if ((rc = run_items(off, m, sp.top, sp.k, nf, ftgt.data(), fP.data(), fz.data(), ffirst.data()))) return rc;
+        if ((rc = finish(c))) return rc;  // (synchronises; a |z| >= 2^31 in an int32 row is reported here)
+    }
+    if (!b.table && !dev) {
+        HIP_TRY(hipMemcpy(b.z_dst, zdev, (size_t)total * d * b.zb, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(b.d_dst, ddev, (size_t)total * 8, hipMemcpyDeviceToHost));
+    }
+    b.listed = true;
+    return LGS_OK;
+}
+
+// offsets, nodes and status of a BallCall to the caller's arrays (host or device)
+int ball_outputs(bool dev, int64_t n, const BallCall& b, int64_t* offsets, int64_t* nodes, int32_t* status) {
+    auto put = [&](void* user, const void* src, size_t bytes) {
+        if (!user) return hipSuccess;
+        if (dev) return hipMemcpy(user, src, bytes, hipMemcpyHostToDevice);
+        memcpy(user, src, bytes);
+        return hipSuccess;
+    };
+    HIP_TRY(put(offsets, b.offsets.data(), (size_t)(n + 1) * 8));
+    HIP_TRY(put(nodes, b.nodes.data(), (size_t)n * 8));
+    HIP_TRY(put(status, b.status.data(), (size_t)n * 4));
+    return LGS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1308,6 +1598,7 @@ int lgs_set_basis(lgs_ctx* c, int64_t d, const double* R, const double* cprime, 
     if ((rc = spec_discard(c))) return rc;  // (a look-ahead launch reads the basis being replaced)
     // another basis skips other panels: every store's clean state starts over
     c->basis_gen += 1;
+    c->has_table = false;  // (lgs_exact_table's: its rows are coefficients of the old basis)
     lgs::qkey_drop(c->qkey);
     for (auto& s : c->bset) lgs::qkey_drop(s.qkey);
     if (c->kstream_split && c->cu_split != 0 && !hook("LGS_PIPE_CU_RESERVE")) {  // the CU split decided anew
@@ -3398,6 +3689,193 @@ int lgs_gaussian_mass(lgs_ctx* c, int64_t n, const double* targets, double sigma
         HIP_TRY(put(o.sum_z ? o.sum_z + (size_t)off * d : nullptr, tz.data(), (size_t)m * d * 8));
     }
     return LGS_OK;
+}
+
+// The points of the ball in traversal order: ball_run's two passes.
+int lgs_ball_points(lgs_ctx* c, int64_t n, const double* targets, const double* radius2, int64_t max_nodes,
+                    int64_t capacity, void* z_out, double* dist2_out, double* cprime_out,
+                    const lgs_ball_outputs* out, uint32_t flags) {
+    TargetCall t{c, n, targets, nullptr, nullptr, cprime_out};
+    int rc = t.open("lgs_ball_points", flags, LGS_DEVICE_PTRS | LGS_COORD_MAJOR | LGS_TARGETS_QFRAME | LGS_Z64);
+    if (rc) return rc;
+    const lgs_ball_outputs none{};
+    const lgs_ball_outputs& o = out ? *out : none;
+    if (c->d > LGS_MASS_MAX_D)
+        return fail(LGS_ERR_INVALID, "lgs_ball_points: d = %lld > LGS_MASS_MAX_D (%d)", (long long)c->d,
+                    LGS_MASS_MAX_D);
+    if (max_nodes < 1 || max_nodes > ((int64_t)1 << 40))
+        return fail(LGS_ERR_INVALID, "max_nodes must be 1..2^40");
+    if (n < 0) return fail(LGS_ERR_INVALID, "n < 0");
+    if (capacity < 0) return fail(LGS_ERR_INVALID, "capacity < 0");
+    if (capacity > 0 && (!z_out || !dist2_out))
+        return fail(LGS_ERR_INVALID, "capacity > 0 needs z_out and dist2_out");
+    BallCall b;
+    if (n == 0) {
+        b.offsets.assign(1, 0);
+        return ball_outputs(t.dev, 0, b, o.offsets, nullptr, nullptr);
+    }
+    if ((rc = t.inputs())) return rc;
+    if (!radius2) return fail(LGS_ERR_INVALID, "null radius2: the ball of lgs_ball_points is finite");
+    std::vector<double> rh, sh;
+    const double* sf;
+    if ((rc = mass_radius_host(c, t.dev, n, radius2, nullptr, rh, sh, b.r, sf))) return rc;
+    b.radius2 = radius2;
+    b.max_nodes = max_nodes;
+    b.capacity = capacity;
+    b.zb = t.ob;
+    b.z_dst = z_out;
+    b.d_dst = dist2_out;
+    if ((rc = ball_run(c, "lgs_ball_points", t, b))) return rc;
+    return ball_outputs(t.dev, n, b, o.offsets, o.nodes, o.status);
+}
+
+// The exact sampler's table: the listed balls of the n targets into the context (ball_run),
+// then the weights and the blocked running sum (exact_scan, timer 8).
+int lgs_exact_table(lgs_ctx* c, int64_t n, const double* targets, double sigma, const double* radius2,
+                    const double* shift, int64_t max_nodes, int64_t max_points, const lgs_exact_table_outputs* out,
+                    uint32_t flags) {
+    TargetCall t{c, n, targets, nullptr, nullptr, nullptr};
+    int rc = t.open("lgs_exact_table", flags, LGS_DEVICE_PTRS | LGS_COORD_MAJOR | LGS_TARGETS_QFRAME | LGS_Z64);
+    if (rc) return rc;
+    const lgs_exact_table_outputs none{};
+    const lgs_exact_table_outputs& o = out ? *out : none;
+    if (c->d > LGS_MASS_MAX_D)
+        return fail(LGS_ERR_INVALID, "lgs_exact_table: d = %lld > LGS_MASS_MAX_D (%d)", (long long)c->d,
+                    LGS_MASS_MAX_D);
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) return fail(LGS_ERR_INVALID, "sigma must be positive and finite");
+    const double two_s2 = 2.0 * sigma * sigma;
+    if (!(two_s2 > 0.0) || !std::isfinite(two_s2)) return fail(LGS_ERR_INVALID, "2 sigma^2 is not a positive fp64");
+    if (max_nodes < 1 || max_nodes > ((int64_t)1 << 40))
+        return fail(LGS_ERR_INVALID, "max_nodes must be 1..2^40");
+    if (n < 1) return fail(LGS_ERR_INVALID, "lgs_exact_table: n < 1");
+    if (max_points < 0) return fail(LGS_ERR_INVALID, "max_points < 0");
+    if ((rc = t.inputs())) return rc;
+    if (!radius2) return fail(LGS_ERR_INVALID, "null radius2: the ball of lgs_exact_table is finite");
+    const bool dev = t.dev;
+    BallCall b;
+    std::vector<double> rh, sh;
+    const double* sf;
+    if ((rc = mass_radius_host(c, dev, n, radius2, shift, rh, sh, b.r, sf))) return rc;
+    c->has_table = false;  // (the table's buffers are about to be rewritten)
+    b.radius2 = radius2;
+    b.max_nodes = max_nodes;
+    b.capacity = max_points;
+    b.zb = t.ob;
+    b.table = true;
+    if ((rc = ball_run(c, "lgs_exact_table", t, b))) return rc;
+    if ((rc = ball_outputs(dev, n, b, o.offsets, o.nodes, o.status))) return rc;
+    const int64_t total = b.offsets[(size_t)n];
+    if (b.bad_status >= 0)
+        return fail(LGS_ERR_INVALID, "lgs_exact_table: target %lld has more than max_nodes nodes (status 1)",
+                    (long long)b.bad_status);
+    if (b.bad_empty >= 0)
+        return fail(LGS_ERR_INVALID, "lgs_exact_table: target %lld has no lattice point in its ball",
+                    (long long)b.bad_empty);
+    if (total > max_points)
+        return fail(LGS_ERR_INVALID, "lgs_exact_table: the balls hold %lld points > max_points = %lld",
+                    (long long)total, (long long)max_points);
+    if (!b.listed) return fail(LGS_ERR_HIP, "lgs_exact_table: the rows were not listed (a library bug)");
+    std::vector<int64_t> boff((size_t)n + 1, 0);
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t rows = b.offsets[(size_t)k + 1] - b.offsets[(size_t)k];
+        boff[(size_t)k + 1] = boff[(size_t)k] + (rows + lgs::kExactBlock - 1) / lgs::kExactBlock;
+    }
+    const int64_t nblocks = boff[(size_t)n];
+    if ((rc = c->TBL_OFF.reserve((size_t)(n + 1) * 8)) || (rc = c->TBL_BOFF.reserve((size_t)(n + 1) * 8)) ||
+        (rc = c->TBL_W.reserve((size_t)total * 8)) || (rc = c->TBL_S.reserve((size_t)total * 8)) ||
+        (rc = c->TBL_BTOT.reserve((size_t)nblocks * 8)) || (rc = c->TBL_BPRE.reserve((size_t)nblocks * 8)) ||
+        (rc = c->TBL_M.reserve((size_t)n * 8)) || (shift && !dev && (rc = c->MASS_SHIFT.reserve((size_t)n * 8))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(c->TBL_OFF.p, b.offsets.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->TBL_BOFF.p, boff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    const double* shift_d = shift;
+    if (shift && !dev) {
+        HIP_TRY(hipMemcpyAsync(c->MASS_SHIFT.p, shift, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        shift_d = c->MASS_SHIFT.as<double>();
+    }
+    lgs::ExactTable tb{};
+    tb.n = n;
+    tb.nblocks = nblocks;
+    tb.off = c->TBL_OFF.as<int64_t>();
+    tb.boff = c->TBL_BOFF.as<int64_t>();
+    tb.D = c->TBL_D.as<double>();
+    tb.W = c->TBL_W.as<double>();
+    tb.S = c->TBL_S.as<double>();
+    tb.btot = c->TBL_BTOT.as<double>();
+    tb.bpre = c->TBL_BPRE.as<double>();
+    tb.mass = c->TBL_M.as<double>();
+    {
+        Scope s(c, 8);
+        HIP_TRY(lgs::launch::exact_scan(tb, shift_d, two_s2, c->stream));
+    }
+    const hipMemcpyKind kind = kind_of(dev, true);
+    if (o.mass) HIP_TRY(hipMemcpyAsync(o.mass, tb.mass, (size_t)n * 8, kind, c->stream));
+    if (o.weights) HIP_TRY(hipMemcpyAsync(o.weights, tb.W, (size_t)total * 8, kind, c->stream));
+    if (o.cum) HIP_TRY(hipMemcpyAsync(o.cum, tb.S, (size_t)total * 8, kind, c->stream));
+    if ((rc = finish(c))) return rc;  // (synchronises: boff and the offsets are host memory)
+    c->has_table = true;
+    c->tbl_n = n;
+    c->tbl_rows = total;
+    c->tbl_zb = t.ob;
+    return LGS_OK;
+}
+
+// K draws per target of the table, chunked like every per-target call: the draw kernel
+// (timer 8) into the compact coordinate-major store, then the caller's rows and B z.
+int lgs_exact_sample(lgs_ctx* c, uint64_t seed, uint64_t first_sample, int64_t n_draws, void* z_out, double* v_out,
+                     const lgs_exact_sample_outputs* out, uint32_t flags) {
+    TargetCall t{c, 0, nullptr, z_out, v_out, nullptr};
+    int rc = t.open("lgs_exact_sample", flags, LGS_DEVICE_PTRS | LGS_Z64);
+    if (rc) return rc;
+    if (n_draws < 0) return fail(LGS_ERR_INVALID, "n_draws < 0");
+    if (!c->has_table) return fail(LGS_ERR_STATE, "no table (lgs_exact_table)");
+    if (n_draws > ((int64_t)1 << 40) / c->tbl_n) return fail(LGS_ERR_INVALID, "more than 2^40 draws in one call");
+    if (v_out && !c->has_B) return fail(LGS_ERR_STATE, "v_out requires B");
+    const lgs_exact_sample_outputs none{};
+    const lgs_exact_sample_outputs& o = out ? *out : none;
+    const int64_t total = c->tbl_n * n_draws;
+    if (total == 0) return LGS_OK;
+    t.n = total;
+    t.qframe = true;  // (no targets: nothing to rotate)
+    const int64_t d = t.d;
+    const int ob = t.ob;
+    const int64_t chunk = std::min<int64_t>(total, c->max_props);
+    const int64_t ldw = (chunk + 63) / 64 * 64;
+    if ((rc = t.begin(chunk, 0)) || (rc = c->DEC_Z.reserve((size_t)ldw * d * ob)) ||
+        (rc = c->CVP_NODES.reserve((size_t)chunk * 8)) || (rc = c->CVP_D2.reserve((size_t)chunk * 8)))
+        return rc;
+    for (int64_t off = 0; off < total; off += chunk) {
+        const int64_t m = t.chunk_at(off, chunk);
+        lgs::ExactDrawArgs a{};
+        a.d = (int)d;
+        a.K = n_draws;
+        a.j0 = off;
+        a.m = m;
+        a.seed = seed;
+        a.first = first_sample;
+        a.off = c->TBL_OFF.as<int64_t>();
+        a.S = c->TBL_S.as<double>();
+        a.D = c->TBL_D.as<double>();
+        a.mass = c->TBL_M.as<double>();
+        a.Z = c->TBL_Z.p;
+        a.W = c->DEC_Z.p;
+        a.ldw = ldw;
+        a.index = o.index ? t.out_ptr(o.index, c->CVP_NODES) : nullptr;
+        a.dist2 = o.dist2 ? t.out_ptr(o.dist2, c->CVP_D2) : nullptr;
+        a.flags = c->flags.as<unsigned int>();
+        // (columns m .. ldw - 1 of the compact store stay zero for B z)
+        HIP_TRY(hipMemsetAsync(a.W, 0, (size_t)ldw * d * ob, c->stream));
+        {
+            Scope s(c, 8);
+            HIP_TRY(lgs::launch::exact_draw(a, c->tbl_zb, ob, c->stream));
+        }
+        c->hist.Z = nullptr;  // (no int16 history: B z reads the compact store)
+        if ((rc = t.z_tail(a.W, ob, ldw)) || (rc = t.out_copy(o.index, (const int64_t*)a.index)) ||
+            (rc = t.out_copy(o.dist2, (const double*)a.dist2)) || (rc = t.v_tail(a.W, ob, ldw)))
+            return rc;
+        if ((rc = finish(c))) return rc;
+    }
+    return finish(c);
 }
 
 }  // extern "C"

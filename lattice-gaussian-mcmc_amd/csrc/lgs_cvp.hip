@@ -237,10 +237,34 @@ __device__ inline void mass_finish(const MassArgs& a, int64_t q, int status, dou
         for (int k = 0; k < a.d; ++k) a.o_sz[(size_t)k * a.ldo + q] = k < a.top ? Sz[k * kCvpLanes] : 0.0;
 }
 
+// The listing pass: the point's row, full coefficients and D.  The row number comes from the
+// counting pass over the same items, so it is below l_rows; the test keeps a store inside the
+// buffers whatever the counts say.
+__device__ inline void mass_list_row(const MassArgs& a, int64_t row, const double* z, double D) {
+    if ((unsigned long long)row >= (unsigned long long)a.l_rows) return;
+    a.l_d[row] = D;
+    if (a.l_zb == 8) {
+        int64_t* o = (int64_t*)a.l_z + (size_t)row * a.d;
+        for (int k = 0; k < a.d; ++k) o[k] = (int64_t)z[k * kCvpLanes];
+    } else {
+        int32_t* o = (int32_t*)a.l_z + (size_t)row * a.d;
+        bool over = false;
+        for (int k = 0; k < a.d; ++k) {
+            const int64_t v = (int64_t)z[k * kCvpLanes];
+            if (v >= (1ll << 31) || v <= -(1ll << 31)) over = true;
+            o[k] = (int32_t)v;
+        }
+        if (over) atomicOr(a.flags, kFlagOverflow);
+    }
+}
+
 // LDS of a block: R (d x d), then base | P | z | sn (| msub | S) of its lanes, laid out as
 // cvp_enum_kernel's.  The sums and counts of the item live in registers between the nodes
-// and in the state block between the launches.
-template <bool MOMENTS>
+// and in the state block between the launches.  LIST (never with MOMENTS): the listing pass
+// of lgs_ball_points -- the same nodes, every point written as row it_first[item] + (points
+// of the item so far) instead of summed; the running count is the state's `points`, so
+// slicing, the hand-out of waiting items and compaction are the counting pass's.
+template <bool MOMENTS, bool LIST>
 __global__ __launch_bounds__(kCvpLanes) void mass_enum_kernel(const MassArgs a) {
     extern __shared__ double lds[];
     const int d = a.d;
@@ -336,14 +360,20 @@ __global__ __launch_bounds__(kCvpLanes) void mass_enum_kernel(const MassArgs a) 
         const double Pi = (i == d - 1 ? 0.0 : P[(i + 1) * kCvpLanes]) + r * r;
         if (Pi < A) {
             if (i == 0) {  // a point of the ball; its siblings at level 0 follow
-                const double w = exp((sh - Pi) / a.two_s2);
-                ++points;
-                dmin = fmin(dmin, Pi);
-                mass = mass + w;
-                energy = energy + w * Pi;
-                if (MOMENTS) {
-                    if (top > 1) msub[kCvpLanes] = msub[kCvpLanes] + w;
-                    Sz[0] = Sz[0] + z[0] * w;
+                if constexpr (LIST) {
+                    mass_list_row(a, a.it_first[q] + points, z, Pi);
+                    ++points;
+                    dmin = fmin(dmin, Pi);
+                } else {
+                    const double w = exp((sh - Pi) / a.two_s2);
+                    ++points;
+                    dmin = fmin(dmin, Pi);
+                    mass = mass + w;
+                    energy = energy + w * Pi;
+                    if (MOMENTS) {
+                        if (top > 1) msub[kCvpLanes] = msub[kCvpLanes] + w;
+                        Sz[0] = Sz[0] + z[0] * w;
+                    }
                 }
             } else {
                 P[i * kCvpLanes] = Pi;
@@ -433,15 +463,33 @@ hipError_t mass_enum(const MassArgs& a, bool moments, hipStream_t st) {
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)((a.nslots + kCvpLanes - 1) / kCvpLanes));
     const size_t lds = mass_lds_bytes(a.d, moments);  // 160 KiB at d = 64; 135 680 B at d = 40 with moments
-    const void* fn = moments ? (const void*)mass_enum_kernel<true> : (const void*)mass_enum_kernel<false>;
+    const void* fn =
+        moments ? (const void*)mass_enum_kernel<true, false> : (const void*)mass_enum_kernel<false, false>;
     if (lds > 48 * 1024) {
         const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     if (moments)
-        hipLaunchKernelGGL(mass_enum_kernel<true>, grid, dim3(kCvpLanes), lds, st, a);
+        hipLaunchKernelGGL((mass_enum_kernel<true, false>), grid, dim3(kCvpLanes), lds, st, a);
     else
-        hipLaunchKernelGGL(mass_enum_kernel<false>, grid, dim3(kCvpLanes), lds, st, a);
+        hipLaunchKernelGGL((mass_enum_kernel<false, false>), grid, dim3(kCvpLanes), lds, st, a);
+    return hipGetLastError();
+}
+
+hipError_t mass_list(const MassArgs& a, hipStream_t st) {
+    if (a.nslots <= 0) return hipSuccess;
+    if (a.d < 1 || a.d > kMassMaxD || a.top < 1 || a.top > a.d || a.nslots > a.S || a.m > a.ldo ||
+        (a.top < a.d && (a.m > a.ldi || !a.it_z || !a.it_P)) || !a.it_tgt || !a.radius2 || !a.it_first ||
+        !a.l_z || !a.l_d || (a.l_zb != 4 && a.l_zb != 8) || a.l_rows < 0)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((a.nslots + kCvpLanes - 1) / kCvpLanes));
+    const size_t lds = mass_lds_bytes(a.d, false);
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void*)mass_enum_kernel<false, true>,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((mass_enum_kernel<false, true>), grid, dim3(kCvpLanes), lds, st, a);
     return hipGetLastError();
 }
 

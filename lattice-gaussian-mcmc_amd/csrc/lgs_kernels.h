@@ -374,6 +374,46 @@ struct MassArgs {
     int32_t* o_status;   // 0 = the item's tree is done, 1 = max_nodes reached, 2 = a non-finite mean
     int64_t ldo;
     unsigned int* flags;
+    // the listing pass (mass_list; lgs_ball_points, lgs_exact_table): point number p of item q
+    // (in the item's traversal order) becomes row it_first[q] + p of l_z (row-major, d elements
+    // of l_zb bytes) and l_d; rows at or beyond l_rows are not written
+    const int64_t* it_first;  // m
+    void* l_z;
+    double* l_d;
+    int l_zb;                 // 4 or 8
+    int64_t l_rows;
+};
+
+// ---- exact sampler: inverse-CDF draws from a listed ball (lgs_exact.hip; lgs_exact_table,
+// lgs_exact_sample).  The table's rows of target t are off[t] .. off[t+1]-1; its blocks of
+// kExactBlock consecutive rows restart at every target: target t owns blocks boff[t] ..
+// boff[t+1]-1 of the call.
+constexpr int kExactBlock = 256;
+struct ExactTable {
+    int64_t n;           // targets
+    int64_t nblocks;     // boff[n]
+    const int64_t* off;  // n + 1
+    const int64_t* boff; // n + 1
+    const double* D;     // rows
+    double* W;           // rows: weights
+    double* S;           // rows: c_m, then S_m
+    double* btot;        // nblocks: c of the block's last row
+    double* bpre;        // nblocks: P_b
+    double* mass;        // n
+};
+struct ExactDrawArgs {
+    int d;
+    int64_t K;           // draws per target
+    int64_t j0, m;       // the chunk: draws j0 .. j0 + m - 1 of the call (draw j: target j / K)
+    uint64_t seed, first;
+    const int64_t* off;
+    const double *S, *D, *mass;
+    const void* Z;       // the table's rows, row-major, tb-byte elements
+    void* W;             // the chunk's coefficients, coordinate-major, ld ldw, ob-byte elements
+    int64_t ldw;
+    int64_t* index;      // m, nullable
+    double* dist2;       // m, nullable
+    unsigned int* flags;
 };
 
 struct AcceptArgs {
@@ -616,8 +656,16 @@ hipError_t cvp_compact(const CvpState& src, const CvpState& dst, int64_t S, cons
 // by at most a.slice nodes and takes the next waiting item when it stops.  moments: the
 // sum_z accumulators (d <= kMassMomentsMaxD).
 hipError_t mass_enum(const MassArgs& a, bool moments, hipStream_t st);
+// The listing pass over the same items: the same traversal, every point written as a row
+// (MassArgs::it_first .. l_rows; it_tgt is required) instead of summed.
+hipError_t mass_list(const MassArgs& a, hipStream_t st);
 hipError_t mass_compact(const MassState& src, const MassState& dst, int64_t S, const int32_t* map, int64_t nlive,
                         int d, bool moments, hipStream_t st);
+// The exact sampler's table (lgs_exact.hip): w and the blocked running sum of every row, in
+// three launches -- weights and c_m per block, P_b and M per target, S_m = P_b + c_m -- and
+// the draws of one chunk (tb / ob: the element widths of the table's rows and of a.W).
+hipError_t exact_scan(const ExactTable& t, const double* shift, double two_s2, hipStream_t st);
+hipError_t exact_draw(const ExactDrawArgs& a, int tb, int ob, hipStream_t st);
 hipError_t round_coeffs(const double* W, int64_t ldw, int d, int64_t n, int zb, void* Z, int64_t ldz,
                         unsigned int* flags, hipStream_t st);
 hipError_t check_range16(const void* zs, int ob, int64_t count, unsigned int* flags, hipStream_t st);

@@ -77,7 +77,8 @@ EXPORTS = ("lgs_version", "lgs_last_error", "lgs_create", "lgs_create_ex", "lgs_
            "lgs_timing_get", "lgs_device_info", "lgs_series_stats", "lgs_gram",
            "lgs_jump_distance", "lgs_marginal_tvd", "lgs_column_range", "lgs_histogram", "lgs_set_decoder", "lgs_nearest_plane",
            "lgs_round_decode", "lgs_counter", "lgs_qskip_elided", "lgs_klein_targets", "lgs_klein_decode",
-           "lgs_imhk_targets", "lgs_closest_vector", "lgs_gaussian_mass")
+           "lgs_imhk_targets", "lgs_closest_vector", "lgs_gaussian_mass", "lgs_ball_points", "lgs_exact_table",
+           "lgs_exact_sample")
 
 
 class ImhkOutputs(ctypes.Structure):
@@ -111,6 +112,22 @@ class MassOutputs(ctypes.Structure):
     _fields_ = [("mass", ctypes.c_void_p), ("energy", ctypes.c_void_p), ("points", ctypes.c_void_p),
                 ("dist2_min", ctypes.c_void_p), ("sum_z", ctypes.c_void_p), ("nodes", ctypes.c_void_p),
                 ("status", ctypes.c_void_p)]
+
+
+class BallOutputs(ctypes.Structure):
+    """struct lgs_ball_outputs (include/lgs.h)."""
+    _fields_ = [("offsets", ctypes.c_void_p), ("nodes", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
+class ExactTableOutputs(ctypes.Structure):
+    """struct lgs_exact_table_outputs (include/lgs.h)."""
+    _fields_ = [("offsets", ctypes.c_void_p), ("nodes", ctypes.c_void_p), ("status", ctypes.c_void_p),
+                ("mass", ctypes.c_void_p), ("weights", ctypes.c_void_p), ("cum", ctypes.c_void_p)]
+
+
+class ExactSampleOutputs(ctypes.Structure):
+    """struct lgs_exact_sample_outputs (include/lgs.h)."""
+    _fields_ = [("index", ctypes.c_void_p), ("dist2", ctypes.c_void_p)]
 
 
 class LgsError(RuntimeError):
@@ -201,6 +218,13 @@ def load_library(path: str = LIB_PATH):
     if hasattr(L, "lgs_gaussian_mass"):  # (older A/B baselines lack it)
         L.lgs_gaussian_mass.argtypes = [_vp, _i64, _vp, ctypes.c_double, _vp, _vp, _i64, _vp,
                                         ctypes.POINTER(MassOutputs), ctypes.c_uint32]
+    if hasattr(L, "lgs_ball_points"):  # (older A/B baselines lack them)
+        L.lgs_ball_points.argtypes = [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.POINTER(BallOutputs),
+                                      ctypes.c_uint32]
+        L.lgs_exact_table.argtypes = [_vp, _i64, _vp, ctypes.c_double, _vp, _vp, _i64, _i64,
+                                      ctypes.POINTER(ExactTableOutputs), ctypes.c_uint32]
+        L.lgs_exact_sample.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, _i64, _vp, _vp,
+                                       ctypes.POINTER(ExactSampleOutputs), ctypes.c_uint32]
     for name in EXPORTS:
         if name not in ("lgs_version", "lgs_last_error") and hasattr(L, name):
             getattr(L, name).restype = ctypes.c_int
@@ -762,6 +786,185 @@ class Context:
         self.gaussian_mass(t, sigma, r2, sh, max_nodes, r["cprime"], r["mass"], r["energy"], r["points"],
                            r["dist2_min"], r["sum_z"], r["nodes"], r["status"], flags)
         return r
+
+    # ---------------------------------------------------------------- the ball's points, the exact sampler
+    _BALL_FLAGS = LGS_DEVICE_PTRS | LGS_COORD_MAJOR | LGS_TARGETS_QFRAME | LGS_Z64
+
+    def _ball_args(self, name, targets, max_nodes, rows, rows_name, flags):
+        """Argument checks of ball_points / exact_table, before any library call."""
+        if isinstance(flags, bool) or not isinstance(flags, (int, np.integer)) or flags & ~self._BALL_FLAGS:
+            raise ValueError(f"{name}: unsupported flags {flags!r}")
+        if self.d > LGS_MASS_MAX_D:
+            raise ValueError(f"{name} supports d <= {LGS_MASS_MAX_D}, the loaded basis has d = {self.d}")
+        if isinstance(max_nodes, bool) or not isinstance(max_nodes, (int, np.integer)) or \
+                not 1 <= max_nodes <= 1 << 40:
+            raise ValueError(f"max_nodes must be an integer in 1..2^40, got {max_nodes!r}")
+        if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or rows < 0:
+            raise ValueError(f"{rows_name} must be a non-negative integer, got {rows!r}")
+        return self._n_targets(targets, flags)
+
+    @staticmethod
+    def _check_shapes(specs):
+        for a, want, name in specs:
+            if a is not None and not isinstance(a, int) and tuple(a.shape) != want:
+                raise ValueError(f"{name}: expected shape {want}, got {tuple(a.shape)}")
+
+    def ball_points(self, targets, radius2, max_nodes=1 << 26, capacity=0, z_out=None, dist2_out=None,
+                    cprime_out=None, offsets=None, nodes=None, status=None, flags=0):
+        """Raw lgs_ball_points on caller buffers (numpy host or device tensors): the lattice
+        points with squared distance below radius2 of each target, in traversal order.
+        targets as in gaussian_mass; radius2 (n,) float64, required; z_out (capacity, d) int32
+        (int64 with LGS_Z64) and dist2_out (capacity,) float64, both None with capacity 0 (the
+        size query); offsets (n + 1,) int64, nodes (n,) int64, status (n,) int32, optional.
+        Rows are written only when offsets[n] <= capacity."""
+        n = self._ball_args("ball_points", targets, max_nodes, capacity, "capacity", flags)
+        if radius2 is None:
+            raise ValueError("radius2 is required: the ball of ball_points is finite")
+        if capacity > 0 and (z_out is None or dist2_out is None):
+            raise ValueError("capacity > 0 needs z_out and dist2_out")
+        zt = "int64" if flags & LGS_Z64 else "int32"
+        _check_bufs(flags, self.device, ((targets, "float64", "targets"), (radius2, "float64", "radius2"),
+                                         (z_out, zt, "z_out"), (dist2_out, "float64", "dist2_out"),
+                                         (cprime_out, "float64", "cprime_out"), (offsets, "int64", "offsets"),
+                                         (nodes, "int64", "nodes"), (status, "int32", "status")))
+        self._check_shapes(((radius2, (n,), "radius2"), (z_out, (capacity, self.d), "z_out"),
+                            (dist2_out, (capacity,), "dist2_out"), (cprime_out, (n, self.d), "cprime_out"),
+                            (offsets, (n + 1,), "offsets"), (nodes, (n,), "nodes"), (status, (n,), "status")))
+        self._ck(self._L.lgs_ball_points(self._h, n, _ptr(targets), _ptr(radius2), int(max_nodes), int(capacity),
+                                         _ptr(z_out) if capacity else None, _ptr(dist2_out) if capacity else None,
+                                         _ptr(cprime_out), _outputs(BallOutputs, offsets, nodes, status), int(flags)))
+
+    def _host_radius(self, n, radius2, name):
+        if radius2 is None:
+            raise ValueError(f"radius2 is required: the ball of {name} is finite")
+        r2 = np.ascontiguousarray(radius2, dtype=np.float64)
+        if r2.shape != (n,) or not np.all((r2 >= 0) & np.isfinite(r2)):
+            raise ValueError(f"radius2 must hold {n} finite non-negative values")
+        return r2
+
+    def ball_points_host(self, targets, radius2, max_nodes=1 << 26, max_points=1 << 24, *, want_cprime=False,
+                         flags=0):
+        """The balls of host targets (n, d) into fresh host arrays {"z" (N, d) int64, "dist2"
+        (N,), "offsets" (n + 1,), "nodes", "status", "cprime"}: a size query, then the listing
+        call (int32 coefficients first, int64 on overflow).  More than max_points points in
+        all is a ValueError."""
+        if isinstance(flags, (int, np.integer)) and not isinstance(flags, bool) and \
+                flags & (LGS_DEVICE_PTRS | LGS_COORD_MAJOR):
+            raise ValueError("ball_points_host takes row-major host targets")
+        t = np.ascontiguousarray(targets, dtype=np.float64)
+        n = self._ball_args("ball_points", t, max_nodes, max_points, "max_points", flags)
+        r2 = self._host_radius(n, radius2, "ball_points")
+        off = np.zeros(n + 1, dtype=np.int64)
+        nd, st = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int32)
+        cp = np.empty((n, self.d)) if want_cprime else None
+        self.ball_points(t, r2, max_nodes, 0, None, None, cp, off, nd, st, flags)
+        total = int(off[n])
+        if total > max_points:
+            raise ValueError(f"the balls hold {total} points > max_points = {max_points}")
+
+        def call(f, zdt):
+            z, d2 = np.empty((total, self.d), dtype=zdt), np.empty(total)
+            if total:
+                self.ball_points(t, r2, max_nodes, total, z, d2, None, off, nd, st, f)
+            return {"z": _z64(z), "dist2": d2, "offsets": off, "nodes": nd, "status": st, "cprime": cp}
+        return _host_retry(flags, call)
+
+    def exact_table(self, targets, sigma, radius2, shift=None, max_nodes=1 << 26, max_points=1 << 24, offsets=None,
+                    nodes=None, status=None, mass=None, weights=None, cum=None, flags=0):
+        """Raw lgs_exact_table on caller buffers: lists the balls of the targets and keeps
+        them in the context, with weights exp((shift - D) / 2 sigma^2) and their blocked
+        running sums, for exact_sample.  offsets (n + 1,) int64, nodes (n,) int64, status (n,)
+        int32, mass (n,) float64, weights / cum (max_points,) float64, all optional.  A target
+        over max_nodes, an empty ball or more than max_points points: LgsError (INVALID) after
+        offsets, nodes and status are filled, and no table is kept."""
+        n = self._ball_args("exact_table", targets, max_nodes, max_points, "max_points", flags)
+        if n < 1:
+            raise ValueError("exact_table needs at least one target")
+        if isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.integer, np.floating)) or \
+                not (sigma > 0 and np.isfinite(sigma)):
+            raise ValueError(f"sigma must be a positive finite number, got {sigma!r}")
+        if radius2 is None:
+            raise ValueError("radius2 is required: the ball of exact_table is finite")
+        _check_bufs(flags & ~LGS_Z64, self.device,
+                    ((targets, "float64", "targets"), (radius2, "float64", "radius2"), (shift, "float64", "shift"),
+                     (offsets, "int64", "offsets"), (nodes, "int64", "nodes"), (status, "int32", "status"),
+                     (mass, "float64", "mass"), (weights, "float64", "weights"), (cum, "float64", "cum")))
+        self._check_shapes(((radius2, (n,), "radius2"), (shift, (n,), "shift"), (offsets, (n + 1,), "offsets"),
+                            (nodes, (n,), "nodes"), (status, (n,), "status"), (mass, (n,), "mass"),
+                            (weights, (max_points,), "weights"), (cum, (max_points,), "cum")))
+        self._table_n = 0
+        self._ck(self._L.lgs_exact_table(self._h, n, _ptr(targets), float(sigma), _ptr(radius2), _ptr(shift),
+                                         int(max_nodes), int(max_points),
+                                         _outputs(ExactTableOutputs, offsets, nodes, status, mass, weights, cum),
+                                         int(flags)))
+        self._table_n = n
+
+    def exact_table_host(self, targets, sigma, radius2, shift=None, max_nodes=1 << 26, max_points=1 << 24, *,
+                         want_weights=False, flags=0):
+        """exact_table of host targets (n, d) into fresh host arrays {"offsets", "nodes",
+        "status", "mass", "weights", "cum"} (the last two None without want_weights; with it a
+        size query by ball_points comes first, so that they hold offsets[n] values)."""
+        if isinstance(flags, (int, np.integer)) and not isinstance(flags, bool) and \
+                flags & (LGS_DEVICE_PTRS | LGS_COORD_MAJOR):
+            raise ValueError("exact_table_host takes row-major host targets")
+        t = np.ascontiguousarray(targets, dtype=np.float64)
+        n = self._ball_args("exact_table", t, max_nodes, max_points, "max_points", flags)
+        r2 = self._host_radius(n, radius2, "exact_table")
+        sh = None
+        if shift is not None:
+            sh = np.ascontiguousarray(shift, dtype=np.float64)
+            if sh.shape != (n,) or not np.all(np.isfinite(sh)):
+                raise ValueError(f"shift must hold {n} finite values")
+        r = {"offsets": np.zeros(n + 1, dtype=np.int64), "nodes": np.empty(n, dtype=np.int64),
+             "status": np.empty(n, dtype=np.int32), "mass": np.empty(n), "weights": None, "cum": None}
+        cap = max_points
+        if want_weights:
+            self.ball_points(t, r2, max_nodes, 0, offsets=r["offsets"], flags=flags)
+            cap = min(max_points, int(r["offsets"][n]))
+            r["weights"], r["cum"] = np.empty(cap), np.empty(cap)
+        self.exact_table(t, sigma, r2, sh, max_nodes, cap, r["offsets"], r["nodes"], r["status"], r["mass"],
+                         r["weights"], r["cum"], flags)
+        return r
+
+    def exact_sample(self, seed, first_sample, n_draws, n_targets, z_out=None, v_out=None, index=None, dist2=None,
+                     flags=0):
+        """Raw lgs_exact_sample on caller buffers: n_draws rows per target of the table, by
+        inverse CDF.  n_targets is the table's target count (the buffers' shapes are checked
+        against it); z_out (n_targets * n_draws, d) int32 / int64, v_out likewise float64, index
+        (n_targets * n_draws,) int64, dist2 likewise float64."""
+        if isinstance(flags, bool) or not isinstance(flags, (int, np.integer)) or \
+                flags & ~(LGS_DEVICE_PTRS | LGS_Z64):
+            raise ValueError(f"exact_sample: unsupported flags {flags!r}")
+        for v, name in ((n_draws, "n_draws"), (n_targets, "n_targets")):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError(f"{name} must be a non-negative integer, got {v!r}")
+        for v, name in ((seed, "seed"), (first_sample, "first_sample")):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < 1 << 64:
+                raise ValueError(f"{name} must be an integer in 0..2^64-1, got {v!r}")
+        total = int(n_targets) * int(n_draws)
+        zt = "int64" if flags & LGS_Z64 else "int32"
+        _check_bufs(flags, self.device, ((z_out, zt, "z_out"), (v_out, "float64", "v_out"),
+                                         (index, "int64", "index"), (dist2, "float64", "dist2")))
+        self._check_shapes(((z_out, (total, self.d), "z_out"), (v_out, (total, self.d), "v_out"),
+                            (index, (total,), "index"), (dist2, (total,), "dist2")))
+        if getattr(self, "_table_n", None) not in (None, 0) and self._table_n != n_targets:
+            raise ValueError(f"the table holds {self._table_n} targets, n_targets = {n_targets}")
+        self._ck(self._L.lgs_exact_sample(self._h, int(seed), int(first_sample), int(n_draws), _ptr(z_out),
+                                          _ptr(v_out), _outputs(ExactSampleOutputs, index, dist2), int(flags)))
+
+    def exact_sample_host(self, seed, first_sample, n_draws, n_targets, *, want_z=True, want_v=True, flags=0):
+        """exact_sample into fresh host arrays {"z", "v", "index", "dist2"} (int32 coefficients
+        first, int64 on overflow: the draws do not depend on the output width)."""
+        if isinstance(flags, (int, np.integer)) and not isinstance(flags, bool) and flags & LGS_DEVICE_PTRS:
+            raise ValueError("exact_sample_host returns host arrays")
+
+        def call(f, zdt):
+            total = int(n_targets) * int(n_draws)
+            z, v, _ = self._host_zvc(total, zdt, want_z, want_v, False)
+            ix, d2 = np.empty(total, dtype=np.int64), np.empty(total)
+            self.exact_sample(seed, first_sample, n_draws, n_targets, z, v, ix, d2, f)
+            return {"z": _z64(z), "v": v, "index": ix, "dist2": d2}
+        return _host_retry(flags, call)
 
     # ---------------------------------------------------------------- diagnostics
     def series_stats(self, x, n_series, n, group_size, group_stride, series_stride, time_stride,

@@ -1,9 +1,10 @@
 """Samplers for lattice Gaussian distributions -- same exports as the reference's
-``src/samplers/__init__.py:3-5``."""
+``src/samplers/__init__.py:3-5``, plus the exact table sampler."""
 from .base import DiscreteGaussianSampler, SamplingStats
 from .klein import RefinedKleinSampler as KleinSampler
 from .klein import RefinedKleinSampler
 from .imhk import IMHKSampler
+from .exact import ExactSampler
 
 __all__ = ["DiscreteGaussianSampler", "KleinSampler", "IMHKSampler", "RefinedKleinSampler",
-           "SamplingStats"]
+           "SamplingStats", "ExactSampler"]
