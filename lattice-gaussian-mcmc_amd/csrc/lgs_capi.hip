@@ -233,6 +233,9 @@ struct lgs_ctx {
     // their weights and running sums, the targets' row and block offsets, the block totals and
     // prefixes, the masses (lgs_set_basis discards it)
     DevBuf TBL_Z, TBL_D, TBL_W, TBL_S, TBL_OFF, TBL_BOFF, TBL_BTOT, TBL_BPRE, TBL_M;
+    // lgs_lll_reduce: the chunk's state blocks, the two live lists, the live counter and range
+    // flag, and (host pointers) the chunk's inputs and outputs
+    DevBuf LLL_ST, LLL_LIVE[2], LLL_CTL, LLL_IO;
     bool has_table = false;
     int64_t tbl_n = 0, tbl_rows = 0;
     int tbl_zb = 4;
@@ -3876,6 +3879,130 @@ int lgs_exact_sample(lgs_ctx* c, uint64_t seed, uint64_t first_sample, int64_t n
         if ((rc = finish(c))) return rc;
     }
     return finish(c);
+}
+
+// LLL reduction of n bases (lgs_lll.hip).  Per chunk of kLllChunk bases: the
+// state blocks from the caller's bases (lll_init), the input range flag read back, then
+// reduction launches of at most `slice` main-loop iterations per basis until the live list --
+// written by each launch, read by the next -- is empty.  Every launch is timer 9.  With host
+// pointers the chunk's inputs and outputs pass through LLL_IO.
+int lgs_lll_reduce(lgs_ctx* c, int64_t n, int64_t d, const int64_t* basis, double delta, double eta,
+                   int64_t max_iters, int64_t* basis_out, int64_t* U_out, const lgs_lll_outputs* out,
+                   uint32_t flags) {
+    if (!c) return fail(LGS_ERR_INVALID, "null context");
+    if (flags & ~(uint32_t)LGS_DEVICE_PTRS) return fail(LGS_ERR_INVALID, "lgs_lll_reduce: unsupported flags 0x%x", flags);
+    if (d < 2 || d > LGS_LLL_MAX_D)
+        return fail(LGS_ERR_INVALID, "lgs_lll_reduce: d = %lld outside 2..LGS_LLL_MAX_D (%d)", (long long)d,
+                    LGS_LLL_MAX_D);
+    if (!(delta > 0.25 && delta < 1.0)) return fail(LGS_ERR_INVALID, "delta must lie in (0.25, 1)");
+    if (!(eta > 0.5 && eta < 1.0)) return fail(LGS_ERR_INVALID, "eta must lie in (0.5, 1)");
+    if (max_iters < 1 || max_iters > ((int64_t)1 << 40)) return fail(LGS_ERR_INVALID, "max_iters must be 1..2^40");
+    if (n < 0) return fail(LGS_ERR_INVALID, "n < 0");
+    if (n == 0) return LGS_OK;
+    if (!basis || !basis_out || !U_out) return fail(LGS_ERR_INVALID, "basis, basis_out and U_out are required");
+    const bool dev = (flags & LGS_DEVICE_PTRS) != 0;
+    const size_t dd = (size_t)d * (size_t)d;
+    if (!dev)
+        for (size_t k = 0; k < (size_t)n * dd; ++k)
+            if (basis[k] >= lgs::kLllMaxB || basis[k] <= -lgs::kLllMaxB)
+                return fail(LGS_ERR_INVALID, "basis %lld: an |entry| >= 2^28", (long long)(k / dd));
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    const lgs_lll_outputs none{};
+    const lgs_lll_outputs& o = out ? *out : none;
+    int64_t slice = lgs::kLllSlice;
+    // (hooks build) LGS_TEST_LLL_SLICE: main-loop iterations per basis and launch -- tests make
+    // every reduction span several launches
+    if (const char* s = hook("LGS_TEST_LLL_SLICE")) slice = std::max<int64_t>(1, atoll(s));
+    const int64_t chunk = std::min<int64_t>(n, lgs::kLllChunk);
+    const size_t words = lgs::lll_state_words((int)d);
+    // LLL_IO (host pointers): basis | basis_out | U_out | swaps | iters | passes | gs_norm2 | status
+    const size_t io_b = (size_t)chunk * dd * 8, io_s = (size_t)chunk * 8, io_g = (size_t)chunk * d * 8;
+    if ((rc = c->LLL_ST.reserve((size_t)chunk * words * 8)) || (rc = c->LLL_LIVE[0].reserve((size_t)chunk * 4)) ||
+        (rc = c->LLL_LIVE[1].reserve((size_t)chunk * 4)) || (rc = c->LLL_CTL.reserve(16)) ||
+        (!dev && (rc = c->LLL_IO.reserve(3 * io_b + 3 * io_s + io_g + (size_t)chunk * 4))))
+        return rc;
+    char* io = c->LLL_IO.as<char>();
+    for (int64_t off = 0; off < n; off += chunk) {
+        const int64_t m = std::min<int64_t>(chunk, n - off);
+        lgs::LllArgs a{};
+        a.d = (int)d;
+        a.m = m;
+        a.slice = slice;
+        a.max_iters = max_iters;
+        a.delta = delta;
+        a.eta = eta;
+        a.state = c->LLL_ST.as<int64_t>();
+        a.ctl = c->LLL_CTL.as<unsigned long long>();
+        a.flags = (unsigned int*)(a.ctl + 1);
+        if (dev) {
+            a.basis = basis + (size_t)off * dd;
+            a.basis_out = basis_out + (size_t)off * dd;
+            a.U_out = U_out + (size_t)off * dd;
+            a.swaps = o.swaps ? o.swaps + off : nullptr;
+            a.iters = o.iters ? o.iters + off : nullptr;
+            a.passes = o.passes ? o.passes + off : nullptr;
+            a.status = o.status ? o.status + off : nullptr;
+            a.gs_norm2 = o.gs_norm2 ? o.gs_norm2 + (size_t)off * d : nullptr;
+        } else {
+            a.basis = (const int64_t*)io;
+            a.basis_out = (int64_t*)(io + io_b);
+            a.U_out = (int64_t*)(io + 2 * io_b);
+            a.swaps = (int64_t*)(io + 3 * io_b);
+            a.iters = (int64_t*)(io + 3 * io_b + io_s);
+            a.passes = (int64_t*)(io + 3 * io_b + 2 * io_s);
+            a.gs_norm2 = (double*)(io + 3 * io_b + 3 * io_s);
+            a.status = (int32_t*)(io + 3 * io_b + 3 * io_s + io_g);
+            HIP_TRY(hipMemcpyAsync(io, basis + (size_t)off * dd, (size_t)m * dd * 8, hipMemcpyHostToDevice, c->stream));
+        }
+        HIP_TRY(hipMemsetAsync(a.ctl, 0, 16, c->stream));
+        {
+            Scope s(c, 9);
+            HIP_TRY(lgs::launch::lll_init(a, c->stream));
+        }
+        unsigned long long cv[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(cv, a.ctl, 16, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if ((unsigned int)cv[1] & lgs::kLllFlagRange) {
+            fold_timers(c);
+            return fail(LGS_ERR_INVALID, "bases %lld..%lld: an |entry| >= 2^28", (long long)off, (long long)(off + m - 1));
+        }
+        // every launch runs `slice` iterations of each live basis or stops it
+        const double bound = std::ceil((double)max_iters / (double)slice) + 2.0;
+        int64_t live = m;
+        int cur = 0;
+        for (double launches = 0.0; live > 0; launches += 1.0) {
+            if (launches > bound) return fail(LGS_ERR_HIP, "lgs_lll_reduce: launch bound exceeded (a library bug)");
+            a.nlive = live;
+            a.live_in = launches == 0.0 ? nullptr : c->LLL_LIVE[cur ^ 1].as<int32_t>();
+            a.live_out = c->LLL_LIVE[cur].as<int32_t>();
+            HIP_TRY(hipMemsetAsync(a.ctl, 0, 8, c->stream));
+            {
+                Scope s(c, 9);
+                HIP_TRY(lgs::launch::lll_reduce(a, c->stream));
+            }
+            HIP_TRY(hipMemcpyAsync(cv, a.ctl, 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (cv[0] > (unsigned long long)live) return fail(LGS_ERR_HIP, "lgs_lll_reduce: live count (a library bug)");
+            live = (int64_t)cv[0];
+            cur ^= 1;
+        }
+        if (!dev) {
+            const auto back = [&](void* dst, const void* src, size_t bytes) {
+                return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+            };
+            HIP_TRY(back(basis_out + (size_t)off * dd, a.basis_out, (size_t)m * dd * 8));
+            HIP_TRY(back(U_out + (size_t)off * dd, a.U_out, (size_t)m * dd * 8));
+            HIP_TRY(back(o.swaps ? o.swaps + off : nullptr, a.swaps, (size_t)m * 8));
+            HIP_TRY(back(o.iters ? o.iters + off : nullptr, a.iters, (size_t)m * 8));
+            HIP_TRY(back(o.passes ? o.passes + off : nullptr, a.passes, (size_t)m * 8));
+            HIP_TRY(back(o.status ? o.status + off : nullptr, a.status, (size_t)m * 4));
+            HIP_TRY(back(o.gs_norm2 ? o.gs_norm2 + (size_t)off * d : nullptr, a.gs_norm2, (size_t)m * d * 8));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+        fold_timers(c);
+    }
+    return LGS_OK;
 }
 
 }  // extern "C"

@@ -299,6 +299,50 @@ struct CvpArgs {
     unsigned int* flags;  // the context's flag words (kFlagNonFinite, kFlagOverflow)
 };
 
+// ---- LLL basis reduction (lgs_lll.hip, lgs_lll_reduce)
+// One basis per block of one wave.  The block's LDS and the basis's state block in device
+// memory have one layout, in 8-byte words, ld = lll_ld(d) (odd: a column sweep by 32 lanes
+// touches 32 different 8-byte bank pairs):
+//   b | U | G | mu   each d x ld: b[i*ld + c] coordinate c of vector i, U likewise (column i
+//                    of the transform), G the int64 Gram matrix, mu the fp64 coefficients
+//   rdiag            kLllLanes words: r[i][i] (0.0 where never computed)
+//   header           kLllHdr words: k, iters, swaps, passes, status (-1 = still running)
+// A launch loads the state, advances the basis by at most `slice` main-loop iterations and
+// stores it back; a basis that stops writes its outputs instead and drops out of the live list.
+constexpr int kLllMaxD = 64;            // LGS_LLL_MAX_D
+constexpr int kLllLanes = 64;           // lanes of a block: one wave
+constexpr int kLllHdr = 8;
+constexpr int64_t kLllSlice = 1 << 12;  // main-loop iterations of a basis per launch at most
+constexpr int64_t kLllChunk = 1024;     // bases of one state block (134 MB at d = 64)
+constexpr int64_t kLllMaxB = (int64_t)1 << 28;  // |b| entries stay below it
+constexpr int64_t kLllMaxU = (int64_t)1 << 40;  // |U| entries
+constexpr double kLllMaxX = 4194304.0;          // 2^22: |X|
+constexpr unsigned int kLllFlagRange = 1u;      // LllArgs::flags: an input |entry| >= 2^28
+__host__ __device__ inline int lll_ld(int d) { return d | 1; }
+__host__ __device__ inline size_t lll_state_words(int d) { return (size_t)4 * d * lll_ld(d) + kLllLanes + kLllHdr; }
+inline size_t lll_lds_bytes(int d) { return lll_state_words(d) * 8; }  // 133 696 B at d = 64
+struct LllArgs {
+    int d;
+    int64_t m;           // bases of the chunk
+    int64_t nlive;       // blocks of this launch
+    const int32_t* live_in;  // nlive basis numbers (nullptr: block q works on basis q)
+    int32_t* live_out;   // the bases still running when the launch ends, in any order
+    unsigned long long* ctl;  // ctl[0]: entries of live_out (zeroed before the launch)
+    int64_t slice;       // main-loop iterations per basis and launch
+    int64_t max_iters;
+    double delta, eta;
+    int64_t* state;      // m state blocks of lll_state_words(d) words
+    const int64_t* basis;  // m x d x d row-major, vector i in column i (lll_init only)
+    int64_t* basis_out;  // m x d x d
+    int64_t* U_out;      // m x d x d
+    int64_t* swaps;      // m (each of the five nullable)
+    int64_t* iters;
+    int64_t* passes;
+    int32_t* status;
+    double* gs_norm2;    // m x d
+    unsigned int* flags;  // one word: kLllFlagRange
+};
+
 // ---- exact Gaussian mass: fixed-radius enumeration (lgs_cvp.hip, lgs_gaussian_mass)
 // The search of lgs_cvp.hip with a bound that never shrinks and a weight on every leaf.  A
 // work item is a partial tree: (target, top, prefix) -- the lane starts on level top - 1
@@ -661,6 +705,12 @@ hipError_t mass_enum(const MassArgs& a, bool moments, hipStream_t st);
 hipError_t mass_list(const MassArgs& a, hipStream_t st);
 hipError_t mass_compact(const MassState& src, const MassState& dst, int64_t S, const int32_t* map, int64_t nlive,
                         int d, bool moments, hipStream_t st);
+// ---- LLL basis reduction (lgs_lll.hip)
+// lll_init: the state blocks of the chunk's m bases from a.basis (Gram matrix, U = I, chol(0),
+// k = 1); an entry out of range sets kLllFlagRange.  lll_reduce: one launch of the reduction
+// over the a.nlive bases of a.live_in.
+hipError_t lll_init(const LllArgs& a, hipStream_t st);
+hipError_t lll_reduce(const LllArgs& a, hipStream_t st);
 // The exact sampler's table (lgs_exact.hip): w and the blocked running sum of every row, in
 // three launches -- weights and c_m per block, P_b and M per target, S_m = P_b + c_m -- and
 // the draws of one chunk (tb / ob: the element widths of the table's rows and of a.W).

@@ -58,6 +58,7 @@ KERNEL_CVP_ENUM = 9  # lgs_closest_vector: the enumeration launches
 LGS_CVP_MAX_D = 64
 LGS_MASS_MAX_D = 64          # lgs_gaussian_mass
 LGS_MASS_MOMENTS_MAX_D = 40  # ... with sum_z
+LGS_LLL_MAX_D = 64           # lgs_lll_reduce (its launches are timer KERNEL_CVP_ENUM too)
 LGS_COUNTER_RESOLVED = 0
 LGS_COUNTER_FALLBACK = 1
 LGS_COUNTER_ACCEPT_RESOLVED = 2
@@ -78,7 +79,7 @@ EXPORTS = ("lgs_version", "lgs_last_error", "lgs_create", "lgs_create_ex", "lgs_
            "lgs_jump_distance", "lgs_marginal_tvd", "lgs_column_range", "lgs_histogram", "lgs_set_decoder", "lgs_nearest_plane",
            "lgs_round_decode", "lgs_counter", "lgs_qskip_elided", "lgs_klein_targets", "lgs_klein_decode",
            "lgs_imhk_targets", "lgs_closest_vector", "lgs_gaussian_mass", "lgs_ball_points", "lgs_exact_table",
-           "lgs_exact_sample")
+           "lgs_exact_sample", "lgs_lll_reduce")
 
 
 class ImhkOutputs(ctypes.Structure):
@@ -128,6 +129,12 @@ class ExactTableOutputs(ctypes.Structure):
 class ExactSampleOutputs(ctypes.Structure):
     """struct lgs_exact_sample_outputs (include/lgs.h)."""
     _fields_ = [("index", ctypes.c_void_p), ("dist2", ctypes.c_void_p)]
+
+
+class LllOutputs(ctypes.Structure):
+    """struct lgs_lll_outputs (include/lgs.h)."""
+    _fields_ = [("swaps", ctypes.c_void_p), ("iters", ctypes.c_void_p), ("passes", ctypes.c_void_p),
+                ("status", ctypes.c_void_p), ("gs_norm2", ctypes.c_void_p)]
 
 
 class LgsError(RuntimeError):
@@ -225,6 +232,9 @@ def load_library(path: str = LIB_PATH):
                                       ctypes.POINTER(ExactTableOutputs), ctypes.c_uint32]
         L.lgs_exact_sample.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, _i64, _vp, _vp,
                                        ctypes.POINTER(ExactSampleOutputs), ctypes.c_uint32]
+    if hasattr(L, "lgs_lll_reduce"):  # (older A/B baselines lack it)
+        L.lgs_lll_reduce.argtypes = [_vp, _i64, _i64, _vp, ctypes.c_double, ctypes.c_double, _i64, _vp, _vp,
+                                     ctypes.POINTER(LllOutputs), ctypes.c_uint32]
     for name in EXPORTS:
         if name not in ("lgs_version", "lgs_last_error") and hasattr(L, name):
             getattr(L, name).restype = ctypes.c_int
@@ -965,6 +975,63 @@ class Context:
             self.exact_sample(seed, first_sample, n_draws, n_targets, z, v, ix, d2, f)
             return {"z": _z64(z), "v": v, "index": ix, "dist2": d2}
         return _host_retry(flags, call)
+
+    # ---------------------------------------------------------------- LLL reduction
+    @staticmethod
+    def _lll_args(basis, delta, eta, max_iters, flags):
+        """Argument checks of lll_reduce / lll_reduce_host, before any library call; returns (n, d)."""
+        if isinstance(flags, bool) or not isinstance(flags, (int, np.integer)) or flags & ~LGS_DEVICE_PTRS:
+            raise ValueError(f"lll_reduce: unsupported flags {flags!r}")
+        shape = tuple(basis.shape)
+        if len(shape) != 3 or shape[1] != shape[2]:
+            raise ValueError(f"basis must have shape (n, d, d), got {shape}")
+        n, d = int(shape[0]), int(shape[1])
+        if not 2 <= d <= LGS_LLL_MAX_D:
+            raise ValueError(f"lll_reduce supports 2 <= d <= {LGS_LLL_MAX_D}, got d = {d}")
+        for name, v, lo, hi in (("delta", delta, 0.25, 1.0), ("eta", eta, 0.5, 1.0)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not lo < v < hi:
+                raise ValueError(f"{name} must lie in ({lo}, {hi}), got {v!r}")
+        if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or \
+                not 1 <= max_iters <= 1 << 40:
+            raise ValueError(f"max_iters must be an integer in 1..2^40, got {max_iters!r}")
+        return n, d
+
+    def lll_reduce(self, basis, basis_out, U_out, delta=0.99, eta=0.51, max_iters=1 << 40, swaps=None, iters=None,
+                   passes=None, status=None, gs_norm2=None, flags=0):
+        """Raw lgs_lll_reduce on caller buffers (numpy host arrays, or device tensors with
+        LGS_DEVICE_PTRS): basis, basis_out, U_out (n, d, d) int64 with vector i in COLUMN i
+        (basis_out = basis @ U_out); swaps, iters, passes (n,) int64, status (n,) int32,
+        gs_norm2 (n, d) float64, all optional.  Needs no loaded basis."""
+        n, d = self._lll_args(basis, delta, eta, max_iters, flags)
+        _check_bufs(flags, self.device, ((basis, "int64", "basis"), (basis_out, "int64", "basis_out"),
+                                         (U_out, "int64", "U_out"), (swaps, "int64", "swaps"),
+                                         (iters, "int64", "iters"), (passes, "int64", "passes"),
+                                         (status, "int32", "status"), (gs_norm2, "float64", "gs_norm2")))
+        if basis_out is None or U_out is None:
+            raise ValueError("basis_out and U_out are required")
+        self._check_shapes(((basis_out, (n, d, d), "basis_out"), (U_out, (n, d, d), "U_out"), (swaps, (n,), "swaps"),
+                            (iters, (n,), "iters"), (passes, (n,), "passes"), (status, (n,), "status"),
+                            (gs_norm2, (n, d), "gs_norm2")))
+        self._ck(self._L.lgs_lll_reduce(self._h, n, d, _ptr(basis), float(delta), float(eta), int(max_iters),
+                                        _ptr(basis_out), _ptr(U_out),
+                                        _outputs(LllOutputs, swaps, iters, passes, status, gs_norm2), int(flags)))
+
+    def lll_reduce_host(self, basis, delta=0.99, eta=0.51, max_iters=1 << 40):
+        """LLL of host bases (n, d, d) int64, vectors in columns, into fresh host arrays
+        {"basis", "U", "swaps", "iters", "passes", "status", "gs_norm2"}."""
+        b = np.ascontiguousarray(basis)
+        if b.dtype != np.int64:
+            raise ValueError(f"basis: expected int64, got {b.dtype}")
+        n, d = self._lll_args(b, delta, eta, max_iters, 0)
+        if np.any(np.abs(b) >= 1 << 28):
+            raise ValueError("basis entries must be below 2^28 in magnitude")
+        out = {"basis": np.empty((n, d, d), dtype=np.int64), "U": np.empty((n, d, d), dtype=np.int64),
+               "swaps": np.empty(n, dtype=np.int64), "iters": np.empty(n, dtype=np.int64),
+               "passes": np.empty(n, dtype=np.int64), "status": np.empty(n, dtype=np.int32),
+               "gs_norm2": np.empty((n, d))}
+        self.lll_reduce(b, out["basis"], out["U"], delta, eta, max_iters, out["swaps"], out["iters"], out["passes"],
+                        out["status"], out["gs_norm2"])
+        return out
 
     # ---------------------------------------------------------------- diagnostics
     def series_stats(self, x, n_series, n, group_size, group_stride, series_stride, time_stride,
