@@ -939,7 +939,10 @@ constexpr uint32_t kSamplerFlags = LGS_DEVICE_PTRS | LGS_Z64 | LGS_COORD_MAJOR |
 // point opens it (context, flag mask), makes its own argument checks where the order of
 // the errors has them (after "n < 0", before an empty call returns), then inputs(); it
 // chooses its chunk geometry and begin()s; per chunk it calls chunk_at(), centres(), its
-// own kernels, the tails of the outputs, and finish(c).
+// own kernels, the tails of the outputs, and finish(c).  The fixed-radius entry points
+// (lgs_gaussian_mass, lgs_ball_points, lgs_exact_table, lgs_exact_sample) open it too; for
+// the first three mass_begin() chooses the geometry and begin()s, and mass_count_chunk() and
+// mass_pass() work on the chunk that chunk_at() set.
 struct TargetCall {
     lgs_ctx* c;
     int64_t n;              // targets of the call
@@ -1182,13 +1185,220 @@ int mass_radius_host(lgs_ctx* c, bool dev, int64_t n, const double* radius2, con
     return LGS_OK;
 }
 
-// The two passes of lgs_ball_points and lgs_exact_table over the machinery of
-// lgs_gaussian_mass.  The counting pass is that call's own -- per chunk the centres (timer 7),
-// the host's split into work items, mass_enum_kernel (timer 9, compaction 8), the items'
-// counts summed per target -- and yields offsets, nodes and status.  The items are emitted
-// in traversal order, so an exclusive prefix of their point counts, in item order, gives
-// every item its first row; the listing pass runs the same items of the complete targets
-// again (those with a point) and writes row first + (points of the item so far).
+// The tuning of the enumerations: nodes per lane and launch, lanes per launch, the depth of
+// the host's split of a fixed-radius tree.  The product library has the constants; the
+// switches of the hooks build are read here and nowhere else -- tests suspend and resume every
+// search, make items wait for a slot, and fix the split (0 = whole trees).
+struct EnumTuning {
+    int64_t slice = lgs::kCvpSlice;
+    int64_t slots = lgs::kCvpMaxSlots;  // (rounded up to whole waves)
+    int force_k = -1;                   // at most d - 1; < 0: the rule of lgs_mass_host.h
+};
+EnumTuning enum_tuning(int64_t d) {
+    EnumTuning u;
+    if (const char* s = hook("LGS_TEST_CVP_SLICE")) u.slice = std::max<int64_t>(1, atoll(s));
+    if (const char* s = hook("LGS_TEST_CVP_SLOTS")) u.slots = std::max<int64_t>(1, atoll(s));
+    if (const char* s = hook("LGS_TEST_MASS_SPLIT"))
+        u.force_k = (int)std::min<int64_t>(std::max<int64_t>(0, atoll(s)), d - 1);
+    u.slots = (u.slots + 63) / 64 * 64;
+    return u;
+}
+
+// What the passes of a fixed-radius call share (lgs_gaussian_mass; ball_run for
+// lgs_ball_points and lgs_exact_table).  The caller fills the first group, mass_begin() the
+// second, ball_run the destination of its listing pass.
+struct MassCall {
+    const char* fn;
+    const double* radius2;  // the caller's (a device array with LGS_DEVICE_PTRS)
+    const double* r;        // the same on the host, checked (mass_radius_host)
+    const double* shift;    // the caller's, nullable
+    int64_t max_nodes;
+    double two_s2;          // (INFINITY: every weight is exp(-0) = 1)
+    bool moments;
+
+    EnumTuning u;
+    bool may_split = false;  // the host splits the trees: it needs R and every chunk's centres
+    int64_t chunk = 0, ldw = 0;
+    std::vector<double> Rh, cph, res;
+
+    void* l_z = nullptr;  // MassArgs::l_*
+    double* l_d = nullptr;
+    int l_zb = 4;
+    int64_t l_rows = 0;
+};
+
+// The first work of a fixed-radius call: the chunk geometry, TargetCall::begin, the scratch
+// that does not depend on the items.
+int mass_begin(lgs_ctx* c, TargetCall& t, MassCall& mc) {
+    const int64_t d = t.d;
+    int rc;
+    mc.u = enum_tuning(d);
+    mc.may_split = mc.u.force_k > 0 || (mc.u.force_k < 0 && t.n < lgs::mass_host::kItemsWanted && d > 1);
+    mc.chunk = std::min<int64_t>(t.n, c->max_props);
+    mc.ldw = (mc.chunk + 63) / 64 * 64;
+    if ((rc = t.begin(mc.chunk, mc.ldw)) || (rc = c->CVP_CTL.reserve(16)) ||
+        (rc = c->CVP_MAP.reserve((size_t)mc.u.slots * 4)) ||
+        (!t.dev && ((rc = c->CVP_RAD.reserve((size_t)mc.chunk * 8)) ||
+                    (mc.shift && (rc = c->MASS_SHIFT.reserve((size_t)mc.chunk * 8))))))
+        return rc;
+    if (mc.may_split) {
+        mc.Rh.resize((size_t)d * d);
+        HIP_TRY(hipMemcpyAsync(mc.Rh.data(), c->R.p, (size_t)d * d * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    return LGS_OK;
+}
+
+// the leading dimension of the per-item arrays: whole waves, at least one
+int64_t mass_ldo(int64_t items) { return (std::max<int64_t>(items, 1) + 63) / 64 * 64; }
+
+// One pass over work items of the chunk t.off .. t.off + t.m - 1, whose centres are in CPT:
+// `items` nodes of level `top` = d - k, item q below the node z[r * items + q] (r < k) of
+// target tgt[q] with partial distance P[q] (k = 0: item q is the whole tree of target q, the
+// arrays are not read).  first = nullptr, a counting pass: mass_enum leaves every item's
+// results in MASS_OUT (lgs::mass_out_at).  Else the listing pass: mass_list writes point p of
+// item q to row first[q] + p of mc.l_z / mc.l_d.  Reserves the state blocks, the results and
+// the item store P | tgt (| first), stages the chunk's radius2 and shift, and runs the launch
+// loop (timer 9, compaction 8).  The host arrays outlive the copies: the loop synchronises.
+int mass_pass(lgs_ctx* c, const TargetCall& t, const MassCall& mc, int top, int k, int64_t items, const int32_t* tgt,
+              const double* P, const double* z, const int64_t* first) {
+    const int64_t d = t.d, off = t.off, m = t.m;
+    const bool moments = mc.moments;
+    int rc;
+    const int64_t ldo = mass_ldo(items);
+    const int64_t S = std::min<int64_t>(ldo, mc.u.slots);
+    const bool store = k > 0 || first;
+    if ((rc = c->CVP_ST[0].reserve(lgs::mass_state_bytes((int)d, S, moments))) ||
+        (rc = c->CVP_ST[1].reserve(lgs::mass_state_bytes((int)d, S, moments))) ||
+        (rc = c->MASS_OUT.reserve(lgs::mass_out_bytes((int)d, ldo, moments))) ||
+        (store && (rc = c->MASS_ITEMS.reserve((size_t)ldo * (first ? 20 : 12)))) ||
+        (k > 0 && (rc = c->MASS_ITZ.reserve((size_t)ldo * k * 8))))
+        return rc;
+    const lgs::MassState st[2] = {lgs::mass_state_at(c->CVP_ST[0].p, (int)d, S, moments),
+                                  lgs::mass_state_at(c->CVP_ST[1].p, (int)d, S, moments)};
+    lgs::MassArgs a{};
+    a.d = (int)d;
+    a.top = top;
+    a.m = items;
+    a.S = S;
+    a.max_nodes = mc.max_nodes;
+    a.slice = mc.u.slice;
+    a.two_s2 = mc.two_s2;
+    a.R = c->R.as<double>();
+    a.CP = c->CPT.as<double>();
+    a.ldc = mc.ldw;
+    if (t.dev) {
+        a.radius2 = mc.radius2 + off;
+        a.shift = mc.shift ? mc.shift + off : nullptr;
+    } else {
+        HIP_TRY(hipMemcpyAsync(c->CVP_RAD.p, mc.radius2 + off, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+        a.radius2 = c->CVP_RAD.as<double>();
+        if (mc.shift) {
+            HIP_TRY(hipMemcpyAsync(c->MASS_SHIFT.p, mc.shift + off, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+            a.shift = c->MASS_SHIFT.as<double>();
+        }
+    }
+    if (store && items > 0) {
+        double* itP = c->MASS_ITEMS.as<double>();
+        int32_t* itT = (int32_t*)(itP + ldo);
+        HIP_TRY(hipMemcpyAsync(itP, P, (size_t)items * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(itT, tgt, (size_t)items * 4, hipMemcpyHostToDevice, c->stream));
+        a.it_P = itP;
+        a.it_tgt = itT;
+        if (k > 0) {
+            HIP_TRY(hipMemcpyAsync(c->MASS_ITZ.p, z, (size_t)items * k * 8, hipMemcpyHostToDevice, c->stream));
+            a.it_z = c->MASS_ITZ.as<double>();
+            a.ldi = items;
+        }
+        if (first) {
+            int64_t* itF = (int64_t*)(itT + ldo);  // (byte 12 ldo: 8-aligned, ldo is whole waves)
+            HIP_TRY(hipMemcpyAsync(itF, first, (size_t)items * 8, hipMemcpyHostToDevice, c->stream));
+            a.it_first = itF;
+        }
+    }
+    if (first) {
+        a.l_z = mc.l_z;
+        a.l_d = mc.l_d;
+        a.l_zb = mc.l_zb;
+        a.l_rows = mc.l_rows;
+    }
+    const lgs::MassItemOut o = lgs::mass_out_at(c->MASS_OUT.p, ldo, moments);
+    a.o_mass = o.mass;
+    a.o_energy = o.energy;
+    a.o_dmin = o.dmin;
+    a.o_points = o.points;
+    a.o_nodes = o.nodes;
+    a.o_status = o.status;
+    a.o_sz = o.sz;
+    a.ldo = ldo;
+    a.ctl = c->CVP_CTL.as<unsigned long long>();
+    a.flags = c->flags.as<unsigned int>();
+    HIP_TRY(hipMemsetAsync(a.ctl, 0, 16, c->stream));
+    HIP_TRY(hipMemsetAsync(st[0].item, 0xff, (size_t)S * 4, c->stream));  // every slot idle
+    int32_t* const ids[2] = {st[0].item, st[1].item};
+    return run_enum_loop(
+        c, mc.fn, items, S, mc.max_nodes, mc.u.slice, a.ctl, ids,
+        [&](int cur, int64_t live) {
+            a.st = st[cur];
+            a.nslots = live;
+            return first ? lgs::launch::mass_list(a, c->stream) : lgs::launch::mass_enum(a, moments, c->stream);
+        },
+        [&](int cur, const int32_t* map, int64_t nlive) {
+            return lgs::launch::mass_compact(st[cur], st[cur ^ 1], S, map, nlive, (int)d, moments, c->stream);
+        });
+}
+
+// The counting step of the chunk t.off .. t.off + t.m - 1: the centres into CPT (timer 7) and,
+// when the host splits, back to it; the trees into work items (lgs_mass_host.h); the counting
+// pass over them; c' to the caller; the items' results to the host, summed per target into
+// `out`.  sp: the split; ipts (nullable): the points of every item, in item order.
+int mass_count_chunk(lgs_ctx* c, TargetCall& t, MassCall& mc, const lgs::mass_host::TargetResults& out,
+                     lgs::mass_host::Split& sp, std::vector<int64_t>* ipts) {
+    namespace mh = lgs::mass_host;
+    const int64_t d = t.d, m = t.m, ldw = mc.ldw;
+    double* X = c->CPT.as<double>();
+    int rc;
+    if ((rc = t.centres(X, ldw))) return rc;
+    if (mc.may_split) {
+        mc.cph.resize((size_t)d * ldw);
+        HIP_TRY(hipMemcpyAsync(mc.cph.data(), X, (size_t)d * ldw * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        sp = mh::split(mc.Rh.data(), (int)d, m, t.n, mc.cph.data(), ldw, mc.r + t.off, mc.u.force_k);
+        if (sp.nonfinite) {
+            if ((rc = finish(c))) return rc;
+            return fail(LGS_ERR_NONFINITE, "non-finite target or conditional mean");
+        }
+    } else {
+        sp = mh::split(nullptr, (int)d, m, t.n, nullptr, ldw, mc.r + t.off, 0);
+    }
+    const int64_t items = sp.items;
+    const int64_t ldo = mass_ldo(items);
+    if ((rc = mass_pass(c, t, mc, sp.top, sp.k, items, sp.tgt.data(), sp.P.data(), sp.z.data(), nullptr))) return rc;
+    if ((rc = t.cprime_tail(X, ldw))) return rc;
+    const size_t out_bytes = lgs::mass_out_bytes((int)d, ldo, mc.moments);
+    mc.res.assign(out_bytes / 8, 0.0);
+    if (items > 0) HIP_TRY(hipMemcpyAsync(mc.res.data(), c->MASS_OUT.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = finish(c))) return rc;  // (synchronises; a lane's non-finite mean is reported here)
+    const lgs::MassItemOut h = lgs::mass_out_at(mc.res.data(), ldo, mc.moments);
+    mh::ItemResults ir{};
+    ir.mass = h.mass;
+    ir.energy = h.energy;
+    ir.dmin = h.dmin;
+    ir.points = h.points;
+    ir.nodes = h.nodes;
+    ir.status = h.status;
+    ir.sz = h.sz;
+    ir.ldo = ldo;
+    mh::combine(sp, mc.max_nodes, ir, out);
+    if (ipts) ipts->assign(ir.points, ir.points + items);
+    return LGS_OK;
+}
+
+// The two passes of lgs_ball_points and lgs_exact_table.  The counting pass is
+// lgs_gaussian_mass's own step, mass_count_chunk, with unit weights, and yields offsets,
+// nodes and status.  The items are emitted in traversal order, so an exclusive prefix of
+// their point counts, in item order, gives every item its first row; the listing pass runs
+// the same items of the complete targets again (those with a point) through mass_pass and
+// writes row first + (points of the item so far).
 struct BallCall {
     const double* radius2 = nullptr;  // the caller's (a device array with LGS_DEVICE_PTRS)
     const double* r = nullptr;        // the same on the host, checked
@@ -1209,105 +1419,10 @@ int ball_run(lgs_ctx* c, const char* fn, TargetCall& t, BallCall& b) {
     const int64_t n = t.n, d = t.d;
     const bool dev = t.dev;
     int rc;
-    int64_t slice = lgs::kCvpSlice, slots = lgs::kCvpMaxSlots;
-    int force_k = -1;
-    // (hooks build) as lgs_gaussian_mass
-    if (const char* s = hook("LGS_TEST_CVP_SLICE")) slice = std::max<int64_t>(1, atoll(s));
-    if (const char* s = hook("LGS_TEST_CVP_SLOTS")) slots = std::max<int64_t>(1, atoll(s));
-    if (const char* s = hook("LGS_TEST_MASS_SPLIT"))
-        force_k = (int)std::min<int64_t>(std::max<int64_t>(0, atoll(s)), d - 1);
-    slots = (slots + 63) / 64 * 64;
-    const bool may_split = force_k > 0 || (force_k < 0 && n < mh::kItemsWanted && d > 1);
-    const int64_t chunk = std::min<int64_t>(n, c->max_props);
-    const int64_t ldw = (chunk + 63) / 64 * 64;
-    if ((rc = t.begin(chunk, ldw)) || (rc = c->CVP_CTL.reserve(16)) || (rc = c->CVP_MAP.reserve((size_t)slots * 4)) ||
-        (!dev && (rc = c->CVP_RAD.reserve((size_t)chunk * 8))))
-        return rc;
-    double* X = c->CPT.as<double>();
-    std::vector<double> Rh, cph, res;
-    if (may_split) {
-        Rh.resize((size_t)d * d);
-        HIP_TRY(hipMemcpyAsync(Rh.data(), c->R.p, (size_t)d * d * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    lgs::MassArgs a{};
-    a.d = (int)d;
-    a.max_nodes = b.max_nodes;
-    a.slice = slice;
-    a.two_s2 = INFINITY;  // (the counting pass's weights are exp(-0) = 1: its mass is not used)
-    a.R = c->R.as<double>();
-    a.CP = X;
-    a.ldc = ldw;
-    a.ctl = c->CVP_CTL.as<unsigned long long>();
-    a.flags = c->flags.as<unsigned int>();
-    // One pass over the items of a chunk (its targets off .. off + m - 1): first = nullptr,
-    // the counting pass; else the listing pass.  The host arrays outlive the copies: the
-    // launch loop synchronises.
-    auto run_items = [&](int64_t off, int64_t m, int top, int k, int64_t items, const int32_t* tgt, const double* P,
-                         const double* z, const int64_t* first) -> int {
-        int rc;
-        const int64_t ldo = (std::max<int64_t>(items, 1) + 63) / 64 * 64;
-        const int64_t S = std::min<int64_t>(ldo, slots);
-        if ((rc = c->CVP_ST[0].reserve(lgs::mass_state_bytes((int)d, S, false))) ||
-            (rc = c->CVP_ST[1].reserve(lgs::mass_state_bytes((int)d, S, false))) ||
-            (rc = c->MASS_OUT.reserve((size_t)ldo * 44)) || (rc = c->MASS_ITEMS.reserve((size_t)ldo * 20)) ||
-            (k > 0 && (rc = c->MASS_ITZ.reserve((size_t)ldo * k * 8))))
-            return rc;
-        const lgs::MassState st[2] = {lgs::mass_state_at(c->CVP_ST[0].p, (int)d, S, false),
-                                      lgs::mass_state_at(c->CVP_ST[1].p, (int)d, S, false)};
-        a.top = top;
-        a.m = items;
-        a.S = S;
-        if (dev) {
-            a.radius2 = b.radius2 + off;
-        } else {
-            HIP_TRY(hipMemcpyAsync(c->CVP_RAD.p, b.radius2 + off, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
-            a.radius2 = c->CVP_RAD.as<double>();
-        }
-        a.it_P = nullptr;
-        a.it_tgt = nullptr;
-        a.it_z = nullptr;
-        a.it_first = nullptr;
-        a.ldi = 0;
-        if (items > 0 && (k > 0 || first)) {
-            double* itP = c->MASS_ITEMS.as<double>();
-            int64_t* itF = (int64_t*)(itP + ldo);
-            int32_t* itT = (int32_t*)(itF + ldo);
-            HIP_TRY(hipMemcpyAsync(itP, P, (size_t)items * 8, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(itT, tgt, (size_t)items * 4, hipMemcpyHostToDevice, c->stream));
-            a.it_P = itP;
-            a.it_tgt = itT;
-            if (k > 0) {
-                HIP_TRY(hipMemcpyAsync(c->MASS_ITZ.p, z, (size_t)items * k * 8, hipMemcpyHostToDevice, c->stream));
-                a.it_z = c->MASS_ITZ.as<double>();
-                a.ldi = items;
-            }
-            if (first) {
-                HIP_TRY(hipMemcpyAsync(itF, first, (size_t)items * 8, hipMemcpyHostToDevice, c->stream));
-                a.it_first = itF;
-            }
-        }
-        a.o_mass = c->MASS_OUT.as<double>();
-        a.o_energy = a.o_mass + ldo;
-        a.o_dmin = a.o_energy + ldo;
-        a.o_points = (int64_t*)(a.o_dmin + ldo);
-        a.o_nodes = a.o_points + ldo;
-        a.o_status = (int32_t*)(a.o_nodes + ldo);
-        a.o_sz = nullptr;
-        a.ldo = ldo;
-        HIP_TRY(hipMemsetAsync(a.ctl, 0, 16, c->stream));
-        HIP_TRY(hipMemsetAsync(st[0].item, 0xff, (size_t)S * 4, c->stream));  // every slot idle
-        int32_t* const ids[2] = {st[0].item, st[1].item};
-        return run_enum_loop(
-            c, fn, items, S, b.max_nodes, slice, a.ctl, ids,
-            [&](int cur, int64_t live) {
-                a.st = st[cur];
-                a.nslots = live;
-                return first ? lgs::launch::mass_list(a, c->stream) : lgs::launch::mass_enum(a, false, c->stream);
-            },
-            [&](int cur, const int32_t* map, int64_t nlive) {
-                return lgs::launch::mass_compact(st[cur], st[cur ^ 1], S, map, nlive, (int)d, false, c->stream);
-            });
-    };
+    // (the counting pass's weights are 1: its mass is not used)
+    MassCall mc{fn, b.radius2, b.r, nullptr, b.max_nodes, INFINITY, false};
+    if ((rc = mass_begin(c, t, mc))) return rc;
+    const int64_t chunk = mc.chunk;
 
     struct Chunk {
         mh::Split sp;
@@ -1321,42 +1436,13 @@ int ball_run(lgs_ctx* c, const char* fn, TargetCall& t, BallCall& b) {
     b.listed = false;
     for (int64_t off = 0; off < n; off += chunk) {  // the counting pass
         const int64_t m = t.chunk_at(off, chunk);
-        if ((rc = t.centres(X, ldw))) return rc;
         chunks.emplace_back();
-        mh::Split& sp = chunks.back().sp;
-        if (may_split) {
-            cph.resize((size_t)d * ldw);
-            HIP_TRY(hipMemcpyAsync(cph.data(), X, (size_t)d * ldw * 8, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            sp = mh::split(Rh.data(), (int)d, m, n, cph.data(), ldw, b.r + off, force_k);
-            if (sp.nonfinite) {
-                if ((rc = finish(c))) return rc;
-                return fail(LGS_ERR_NONFINITE, "non-finite target or conditional mean");
-            }
-        } else {
-            sp = mh::split(nullptr, (int)d, m, n, nullptr, ldw, b.r + off, 0);
-        }
-        const int64_t items = sp.items;
-        const int64_t ldo = (std::max<int64_t>(items, 1) + 63) / 64 * 64;
-        if ((rc = run_items(off, m, sp.top, sp.k, items, sp.tgt.data(), sp.P.data(), sp.z.data(), nullptr))) return rc;
-        if ((rc = t.cprime_tail(X, ldw))) return rc;
-        res.assign((size_t)ldo * 44 / 8, 0.0);
-        if (items > 0)
-            HIP_TRY(hipMemcpyAsync(res.data(), c->MASS_OUT.p, (size_t)ldo * 44, hipMemcpyDeviceToHost, c->stream));
-        if ((rc = finish(c))) return rc;  // (synchronises; a lane's non-finite mean is reported here)
-        mh::ItemResults ir{};
-        ir.mass = res.data();
-        ir.energy = ir.mass + ldo;
-        ir.dmin = ir.energy + ldo;
-        ir.points = (const int64_t*)(ir.dmin + ldo);
-        ir.nodes = ir.points + ldo;
-        ir.status = (const int32_t*)(ir.nodes + ldo);
-        ir.ldo = ldo;
         std::vector<double> tm((size_t)m), te((size_t)m), td((size_t)m);
-        mh::combine(sp, b.max_nodes, ir,
-                    mh::TargetResults{tm.data(), te.data(), td.data(), nullptr, tpts.data() + off, b.nodes.data() + off,
-                                      b.status.data() + off});
-        chunks.back().ipts.assign(ir.points, ir.points + items);
+        if ((rc = mass_count_chunk(c, t, mc,
+                                   mh::TargetResults{tm.data(), te.data(), td.data(), nullptr, tpts.data() + off,
+                                                     b.nodes.data() + off, b.status.data() + off},
+                                   chunks.back().sp, &chunks.back().ipts)))
+            return rc;
     }
     b.bad_status = b.bad_empty = -1;
     for (int64_t k = 0; k < n; ++k) {
@@ -1380,10 +1466,10 @@ int ball_run(lgs_ctx* c, const char* fn, TargetCall& t, BallCall& b) {
         zdev = c->BALL_Z.p;
         ddev = c->BALL_D.as<double>();
     }
-    a.l_z = zdev;
-    a.l_d = ddev;
-    a.l_zb = b.zb;
-    a.l_rows = total;
+    mc.l_z = zdev;
+    mc.l_d = ddev;
+    mc.l_zb = b.zb;
+    mc.l_rows = total;
     std::vector<int32_t> ftgt;
     std::vector<double> fP, fz;
     std::vector<int64_t> ffirst, fq, run;
@@ -1411,8 +1497,9 @@ int ball_run(lgs_ctx* c, const char* fn, TargetCall& t, BallCall& b) {
         fz.resize((size_t)nf * sp.k);
         for (int r = 0; r < sp.k; ++r)
             for (int64_t j = 0; j < nf; ++j) fz[(size_t)r * nf + j] = sp.z[(size_t)r * sp.items + fq[(size_t)j]];
-        if (chunks.size() > 1 && (rc = t.centres(X, ldw))) return rc;  // (one chunk: X still holds its centres)
-        if ((rc = run_items(off, m, sp.top, sp.k, nf, ftgt.data(), fP.data(), fz.data(), ffirst.data()))) return rc;
+        // (one chunk: CPT still holds its centres)
+        if (chunks.size() > 1 && (rc = t.centres(c->CPT.as<double>(), mc.ldw))) return rc;
+        if ((rc = mass_pass(c, t, mc, sp.top, sp.k, nf, ftgt.data(), fP.data(), fz.data(), ffirst.data()))) return rc;
         if ((rc = finish(c))) return rc;  // (synchronises; a |z| >= 2^31 in an int32 row is reported here)
     }
     if (!b.table && !dev) {
@@ -1423,17 +1510,31 @@ int ball_run(lgs_ctx* c, const char* fn, TargetCall& t, BallCall& b) {
     return LGS_OK;
 }
 
+// a host array to the caller's array, host or device (null: not wanted)
+hipError_t put(bool dev, void* user, const void* src, size_t bytes) {
+    if (!user) return hipSuccess;
+    if (dev) return hipMemcpy(user, src, bytes, hipMemcpyHostToDevice);
+    memcpy(user, src, bytes);
+    return hipSuccess;
+}
+
+// The checks of max_nodes and sigma that the exact entry points share.
+int check_max_nodes(int64_t max_nodes) {
+    if (max_nodes < 1 || max_nodes > ((int64_t)1 << 40)) return fail(LGS_ERR_INVALID, "max_nodes must be 1..2^40");
+    return LGS_OK;
+}
+int sigma_two_s2(double sigma, double& two_s2) {
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) return fail(LGS_ERR_INVALID, "sigma must be positive and finite");
+    two_s2 = 2.0 * sigma * sigma;
+    if (!(two_s2 > 0.0) || !std::isfinite(two_s2)) return fail(LGS_ERR_INVALID, "2 sigma^2 is not a positive fp64");
+    return LGS_OK;
+}
+
 // offsets, nodes and status of a BallCall to the caller's arrays (host or device)
 int ball_outputs(bool dev, int64_t n, const BallCall& b, int64_t* offsets, int64_t* nodes, int32_t* status) {
-    auto put = [&](void* user, const void* src, size_t bytes) {
-        if (!user) return hipSuccess;
-        if (dev) return hipMemcpy(user, src, bytes, hipMemcpyHostToDevice);
-        memcpy(user, src, bytes);
-        return hipSuccess;
-    };
-    HIP_TRY(put(offsets, b.offsets.data(), (size_t)(n + 1) * 8));
-    HIP_TRY(put(nodes, b.nodes.data(), (size_t)n * 8));
-    HIP_TRY(put(status, b.status.data(), (size_t)n * 4));
+    HIP_TRY(put(dev, offsets, b.offsets.data(), (size_t)(n + 1) * 8));
+    HIP_TRY(put(dev, nodes, b.nodes.data(), (size_t)n * 8));
+    HIP_TRY(put(dev, status, b.status.data(), (size_t)n * 4));
     return LGS_OK;
 }
 
@@ -3400,8 +3501,7 @@ int lgs_closest_vector(lgs_ctx* c, int64_t n, const double* targets, const doubl
     if (c->d > LGS_CVP_MAX_D)
         return fail(LGS_ERR_INVALID, "lgs_closest_vector: d = %lld > LGS_CVP_MAX_D (%d)", (long long)c->d,
                     LGS_CVP_MAX_D);
-    if (max_nodes < 1 || max_nodes > ((int64_t)1 << 40))
-        return fail(LGS_ERR_INVALID, "max_nodes must be 1..2^40");
+    if ((rc = check_max_nodes(max_nodes))) return rc;
     if (n < 0) return fail(LGS_ERR_INVALID, "n < 0");
     if (n == 0) return LGS_OK;
     if ((rc = t.inputs())) return rc;
@@ -3422,15 +3522,11 @@ int lgs_closest_vector(lgs_ctx* c, int64_t n, const double* targets, const doubl
     const lgs_cvp_outputs& o = out ? *out : none;
     const int64_t d = t.d;
     const int ob = t.ob;
-    int64_t slice = lgs::kCvpSlice, slots = lgs::kCvpMaxSlots;
-    // (hooks build) LGS_TEST_CVP_SLICE / LGS_TEST_CVP_SLOTS: nodes per lane and launch, lanes
-    // per launch (rounded up to whole waves) -- tests suspend and resume every search, and
-    // make targets wait for a slot
-    if (const char* s = hook("LGS_TEST_CVP_SLICE")) slice = std::max<int64_t>(1, atoll(s));
-    if (const char* s = hook("LGS_TEST_CVP_SLOTS")) slots = std::max<int64_t>(1, atoll(s));
+    const EnumTuning u = enum_tuning(d);
+    const int64_t slice = u.slice;
     const int64_t chunk = std::min<int64_t>(n, c->max_props);
     const int64_t ldw = (chunk + 63) / 64 * 64;
-    const int64_t S = std::min<int64_t>(ldw, (slots + 63) / 64 * 64);
+    const int64_t S = std::min<int64_t>(ldw, u.slots);
     if ((rc = t.begin(chunk, ldw)) || (rc = c->DEC_Z.reserve((size_t)ldw * d * ob)) ||
         (rc = c->CVP_ST[0].reserve(lgs::cvp_state_bytes((int)d, S))) ||
         (rc = c->CVP_ST[1].reserve(lgs::cvp_state_bytes((int)d, S))) || (rc = c->CVP_CTL.reserve(16)) ||
@@ -3496,11 +3592,12 @@ int lgs_closest_vector(lgs_ctx* c, int64_t n, const double* targets, const doubl
 }
 
 // Exact Gaussian mass: lgs_closest_vector's search with a fixed radius and a weight on every
-// point (mass_enum_kernel, lgs_cvp.hip).  Per chunk of max_proposals targets:
-// the centres into CPT (timer 7) and, unless the call has 2^14 targets, back to the host,
-// which splits every tree into work items (lgs_mass_host.h); the enumeration of the items
-// (timer 9) with lgs_closest_vector's launch loop -- slices, hand-out of waiting items,
-// compaction (timer 8); the items' results to the host, summed per target, to the caller.
+// point (mass_enum_kernel, lgs_cvp.hip).  The argument checks, then per chunk
+// of max_proposals targets the counting step that ball_run shares (mass_count_chunk): the
+// centres into CPT (timer 7) and, unless the call has 2^14 targets, back to the host, which
+// splits every tree into work items (lgs_mass_host.h); the pass over the items (mass_pass:
+// timer 9, lgs_closest_vector's launch loop -- slices, hand-out of waiting items, compaction,
+// timer 8); the items' results to the host, summed per target.  The sums go to the caller here.
 int lgs_gaussian_mass(lgs_ctx* c, int64_t n, const double* targets, double sigma, const double* radius2,
                       const double* shift, int64_t max_nodes, double* cprime_out, const lgs_mass_outputs* out,
                       uint32_t flags) {
@@ -3517,179 +3614,38 @@ int lgs_gaussian_mass(lgs_ctx* c, int64_t n, const double* targets, double sigma
     if (moments && c->d > LGS_MASS_MOMENTS_MAX_D)
         return fail(LGS_ERR_INVALID, "lgs_gaussian_mass: sum_z needs d <= LGS_MASS_MOMENTS_MAX_D (%d), d = %lld",
                     LGS_MASS_MOMENTS_MAX_D, (long long)c->d);
-    if (!(sigma > 0.0) || !std::isfinite(sigma)) return fail(LGS_ERR_INVALID, "sigma must be positive and finite");
-    const double two_s2 = 2.0 * sigma * sigma;
-    if (!(two_s2 > 0.0) || !std::isfinite(two_s2)) return fail(LGS_ERR_INVALID, "2 sigma^2 is not a positive fp64");
-    if (max_nodes < 1 || max_nodes > ((int64_t)1 << 40))
-        return fail(LGS_ERR_INVALID, "max_nodes must be 1..2^40");
+    double two_s2;
+    if ((rc = sigma_two_s2(sigma, two_s2)) || (rc = check_max_nodes(max_nodes))) return rc;
     if (n < 0) return fail(LGS_ERR_INVALID, "n < 0");
     if (n == 0) return LGS_OK;
     if ((rc = t.inputs())) return rc;
     if (!radius2) return fail(LGS_ERR_INVALID, "null radius2: the ball of lgs_gaussian_mass is finite");
     const bool dev = t.dev;
-    // radius2 and shift on the host: the checks are the host's, and so is the split
     std::vector<double> rh, sh;
-    const double* r = radius2;
-    const double* sf = shift;
-    if (dev) {
-        rh.resize((size_t)n);
-        HIP_TRY(hipMemcpyAsync(rh.data(), radius2, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-        if (shift) {
-            sh.resize((size_t)n);
-            HIP_TRY(hipMemcpyAsync(sh.data(), shift, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-            sf = sh.data();
-        }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        r = rh.data();
-    }
-    for (int64_t k = 0; k < n; ++k) {
-        if (!(r[k] >= 0.0) || !std::isfinite(r[k]))
-            return fail(LGS_ERR_INVALID, "radius2[%lld] is negative or not finite", (long long)k);
-        if (sf && !std::isfinite(sf[k])) return fail(LGS_ERR_INVALID, "shift[%lld] is not finite", (long long)k);
-    }
+    const double *r, *sf;
+    if ((rc = mass_radius_host(c, dev, n, radius2, shift, rh, sh, r, sf))) return rc;
     const int64_t d = t.d;
-    int64_t slice = lgs::kCvpSlice, slots = lgs::kCvpMaxSlots;
-    int force_k = -1;
-    // (hooks build) lgs_closest_vector's LGS_TEST_CVP_SLICE / LGS_TEST_CVP_SLOTS, and
-    // LGS_TEST_MASS_SPLIT = k: the depth of the split, 0 = whole trees
-    if (const char* s = hook("LGS_TEST_CVP_SLICE")) slice = std::max<int64_t>(1, atoll(s));
-    if (const char* s = hook("LGS_TEST_CVP_SLOTS")) slots = std::max<int64_t>(1, atoll(s));
-    if (const char* s = hook("LGS_TEST_MASS_SPLIT"))
-        force_k = (int)std::min<int64_t>(std::max<int64_t>(0, atoll(s)), d - 1);
-    slots = (slots + 63) / 64 * 64;
-    const bool may_split = force_k > 0 || (force_k < 0 && n < mh::kItemsWanted && d > 1);
-    const int64_t chunk = std::min<int64_t>(n, c->max_props);
-    const int64_t ldw = (chunk + 63) / 64 * 64;
-    if ((rc = t.begin(chunk, ldw)) || (rc = c->CVP_CTL.reserve(16)) || (rc = c->CVP_MAP.reserve((size_t)slots * 4)) ||
-        (!dev && ((rc = c->CVP_RAD.reserve((size_t)chunk * 8)) ||
-                  (shift && (rc = c->MASS_SHIFT.reserve((size_t)chunk * 8))))))
-        return rc;
-    double* X = c->CPT.as<double>();
-    std::vector<double> Rh, cph, res;
-    if (may_split) {
-        Rh.resize((size_t)d * d);
-        HIP_TRY(hipMemcpyAsync(Rh.data(), c->R.p, (size_t)d * d * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    for (int64_t off = 0; off < n; off += chunk) {
-        const int64_t m = t.chunk_at(off, chunk);
-        if ((rc = t.centres(X, ldw))) return rc;
-        mh::Split sp;
-        if (may_split) {
-            cph.resize((size_t)d * ldw);
-            HIP_TRY(hipMemcpyAsync(cph.data(), X, (size_t)d * ldw * 8, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            sp = mh::split(Rh.data(), (int)d, m, n, cph.data(), ldw, r + off, force_k);
-            if (sp.nonfinite) {
-                if ((rc = finish(c))) return rc;
-                return fail(LGS_ERR_NONFINITE, "non-finite target or conditional mean");
-            }
-        } else {
-            sp = mh::split(nullptr, (int)d, m, n, nullptr, ldw, r + off, 0);
-        }
-        const int64_t items = sp.items;
-        const int64_t ldo = (std::max<int64_t>(items, 1) + 63) / 64 * 64;
-        const int64_t S = std::min<int64_t>(ldo, slots);
-        const size_t out_bytes = (size_t)ldo * (44 + (moments ? (size_t)d * 8 : 0));
-        if ((rc = c->CVP_ST[0].reserve(lgs::mass_state_bytes((int)d, S, moments))) ||
-            (rc = c->CVP_ST[1].reserve(lgs::mass_state_bytes((int)d, S, moments))) ||
-            (rc = c->MASS_OUT.reserve(out_bytes)) ||
-            (sp.k > 0 && ((rc = c->MASS_ITEMS.reserve((size_t)ldo * 12)) ||
-                          (rc = c->MASS_ITZ.reserve((size_t)ldo * sp.k * 8)))))
-            return rc;
-        const lgs::MassState st[2] = {lgs::mass_state_at(c->CVP_ST[0].p, (int)d, S, moments),
-                                      lgs::mass_state_at(c->CVP_ST[1].p, (int)d, S, moments)};
-        lgs::MassArgs a{};
-        a.d = (int)d;
-        a.top = sp.top;
-        a.m = items;
-        a.S = S;
-        a.max_nodes = max_nodes;
-        a.slice = slice;
-        a.two_s2 = two_s2;
-        a.R = c->R.as<double>();
-        a.CP = X;
-        a.ldc = ldw;
-        if (dev) {
-            a.radius2 = radius2 + off;
-            a.shift = shift ? shift + off : nullptr;
-        } else {
-            HIP_TRY(hipMemcpyAsync(c->CVP_RAD.p, radius2 + off, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
-            a.radius2 = c->CVP_RAD.as<double>();
-            if (shift) {
-                HIP_TRY(hipMemcpyAsync(c->MASS_SHIFT.p, shift + off, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
-                a.shift = c->MASS_SHIFT.as<double>();
-            }
-        }
-        if (sp.k > 0 && items > 0) {  // (sp outlives the copies: the launch loop synchronises)
-            double* itP = c->MASS_ITEMS.as<double>();
-            int32_t* itT = (int32_t*)(itP + ldo);
-            HIP_TRY(hipMemcpyAsync(itP, sp.P.data(), (size_t)items * 8, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(itT, sp.tgt.data(), (size_t)items * 4, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->MASS_ITZ.p, sp.z.data(), (size_t)items * sp.k * 8, hipMemcpyHostToDevice,
-                                   c->stream));
-            a.it_P = itP;
-            a.it_tgt = itT;
-            a.it_z = c->MASS_ITZ.as<double>();
-            a.ldi = items;
-        }
-        a.ctl = c->CVP_CTL.as<unsigned long long>();
-        a.o_mass = c->MASS_OUT.as<double>();
-        a.o_energy = a.o_mass + ldo;
-        a.o_dmin = a.o_energy + ldo;
-        a.o_points = (int64_t*)(a.o_dmin + ldo);
-        a.o_nodes = a.o_points + ldo;
-        a.o_status = (int32_t*)(a.o_nodes + ldo);
-        a.o_sz = moments ? (double*)((char*)c->MASS_OUT.p + (size_t)ldo * 44) : nullptr;
-        a.ldo = ldo;
-        a.flags = c->flags.as<unsigned int>();
-        HIP_TRY(hipMemsetAsync(a.ctl, 0, 16, c->stream));
-        HIP_TRY(hipMemsetAsync(st[0].item, 0xff, (size_t)S * 4, c->stream));  // every slot idle
-        int32_t* const ids[2] = {st[0].item, st[1].item};
-        if ((rc = run_enum_loop(
-                 c, "lgs_gaussian_mass", items, S, max_nodes, slice, a.ctl, ids,
-                 [&](int cur, int64_t live) {
-                     a.st = st[cur];
-                     a.nslots = live;
-                     return lgs::launch::mass_enum(a, moments, c->stream);
-                 },
-                 [&](int cur, const int32_t* map, int64_t nlive) {
-                     return lgs::launch::mass_compact(st[cur], st[cur ^ 1], S, map, nlive, (int)d, moments, c->stream);
-                 })))
-            return rc;
-        if ((rc = t.cprime_tail(X, ldw))) return rc;
-        res.assign(out_bytes / 8, 0.0);
-        if (items > 0)
-            HIP_TRY(hipMemcpyAsync(res.data(), c->MASS_OUT.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-        if ((rc = finish(c))) return rc;  // (synchronises; a lane's non-finite mean is reported here)
-        mh::ItemResults ir{};
-        ir.mass = res.data();
-        ir.energy = ir.mass + ldo;
-        ir.dmin = ir.energy + ldo;
-        ir.points = (const int64_t*)(ir.dmin + ldo);
-        ir.nodes = ir.points + ldo;
-        ir.status = (const int32_t*)(ir.nodes + ldo);
-        ir.sz = moments ? (const double*)((const char*)res.data() + (size_t)ldo * 44) : nullptr;
-        ir.ldo = ldo;
+    MassCall mc{"lgs_gaussian_mass", radius2, r, shift, max_nodes, two_s2, moments};
+    if ((rc = mass_begin(c, t, mc))) return rc;
+    for (int64_t off = 0; off < n; off += mc.chunk) {
+        const int64_t m = t.chunk_at(off, mc.chunk);
         std::vector<double> tm((size_t)m), te((size_t)m), td((size_t)m), tz(moments ? (size_t)m * d : 0);
         std::vector<int64_t> tp((size_t)m), tn((size_t)m);
         std::vector<int32_t> ts((size_t)m);
-        mh::combine(sp, max_nodes, ir,
-                    mh::TargetResults{tm.data(), te.data(), td.data(), moments ? tz.data() : nullptr, tp.data(),
-                                      tn.data(), ts.data()});
+        mh::Split sp;
+        if ((rc = mass_count_chunk(c, t, mc,
+                                   mh::TargetResults{tm.data(), te.data(), td.data(), moments ? tz.data() : nullptr,
+                                                     tp.data(), tn.data(), ts.data()},
+                                   sp, nullptr)))
+            return rc;
         // (the sums are the host's: to the caller's arrays, device or host)
-        auto put = [&](void* user, const void* src, size_t bytes) {
-            if (!user) return hipSuccess;
-            if (dev) return hipMemcpy(user, src, bytes, hipMemcpyHostToDevice);
-            memcpy(user, src, bytes);
-            return hipSuccess;
-        };
-        HIP_TRY(put(o.mass ? o.mass + off : nullptr, tm.data(), (size_t)m * 8));
-        HIP_TRY(put(o.energy ? o.energy + off : nullptr, te.data(), (size_t)m * 8));
-        HIP_TRY(put(o.dist2_min ? o.dist2_min + off : nullptr, td.data(), (size_t)m * 8));
-        HIP_TRY(put(o.points ? o.points + off : nullptr, tp.data(), (size_t)m * 8));
-        HIP_TRY(put(o.nodes ? o.nodes + off : nullptr, tn.data(), (size_t)m * 8));
-        HIP_TRY(put(o.status ? o.status + off : nullptr, ts.data(), (size_t)m * 4));
-        HIP_TRY(put(o.sum_z ? o.sum_z + (size_t)off * d : nullptr, tz.data(), (size_t)m * d * 8));
+        HIP_TRY(put(dev, o.mass ? o.mass + off : nullptr, tm.data(), (size_t)m * 8));
+        HIP_TRY(put(dev, o.energy ? o.energy + off : nullptr, te.data(), (size_t)m * 8));
+        HIP_TRY(put(dev, o.dist2_min ? o.dist2_min + off : nullptr, td.data(), (size_t)m * 8));
+        HIP_TRY(put(dev, o.points ? o.points + off : nullptr, tp.data(), (size_t)m * 8));
+        HIP_TRY(put(dev, o.nodes ? o.nodes + off : nullptr, tn.data(), (size_t)m * 8));
+        HIP_TRY(put(dev, o.status ? o.status + off : nullptr, ts.data(), (size_t)m * 4));
+        HIP_TRY(put(dev, o.sum_z ? o.sum_z + (size_t)off * d : nullptr, tz.data(), (size_t)m * d * 8));
     }
     return LGS_OK;
 }
@@ -3706,8 +3662,7 @@ int lgs_ball_points(lgs_ctx* c, int64_t n, const double* targets, const double* 
     if (c->d > LGS_MASS_MAX_D)
         return fail(LGS_ERR_INVALID, "lgs_ball_points: d = %lld > LGS_MASS_MAX_D (%d)", (long long)c->d,
                     LGS_MASS_MAX_D);
-    if (max_nodes < 1 || max_nodes > ((int64_t)1 << 40))
-        return fail(LGS_ERR_INVALID, "max_nodes must be 1..2^40");
+    if ((rc = check_max_nodes(max_nodes))) return rc;
     if (n < 0) return fail(LGS_ERR_INVALID, "n < 0");
     if (capacity < 0) return fail(LGS_ERR_INVALID, "capacity < 0");
     if (capacity > 0 && (!z_out || !dist2_out))
@@ -3745,11 +3700,8 @@ int lgs_exact_table(lgs_ctx* c, int64_t n, const double* targets, double sigma, 
     if (c->d > LGS_MASS_MAX_D)
         return fail(LGS_ERR_INVALID, "lgs_exact_table: d = %lld > LGS_MASS_MAX_D (%d)", (long long)c->d,
                     LGS_MASS_MAX_D);
-    if (!(sigma > 0.0) || !std::isfinite(sigma)) return fail(LGS_ERR_INVALID, "sigma must be positive and finite");
-    const double two_s2 = 2.0 * sigma * sigma;
-    if (!(two_s2 > 0.0) || !std::isfinite(two_s2)) return fail(LGS_ERR_INVALID, "2 sigma^2 is not a positive fp64");
-    if (max_nodes < 1 || max_nodes > ((int64_t)1 << 40))
-        return fail(LGS_ERR_INVALID, "max_nodes must be 1..2^40");
+    double two_s2;
+    if ((rc = sigma_two_s2(sigma, two_s2)) || (rc = check_max_nodes(max_nodes))) return rc;
     if (n < 1) return fail(LGS_ERR_INVALID, "lgs_exact_table: n < 1");
     if (max_points < 0) return fail(LGS_ERR_INVALID, "max_points < 0");
     if ((rc = t.inputs())) return rc;

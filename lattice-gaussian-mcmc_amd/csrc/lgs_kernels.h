@@ -392,6 +392,28 @@ inline MassState mass_state_at(void* p, int d, int64_t S, bool moments) {  // (S
     s.lvl = s.item + S;
     return s;
 }
+// The per-item results of one pass, on the device and in the host's copy: mass | energy | dmin
+// | points | nodes | status of ldo items each, 44 bytes per item, then sz (moments: d x ldo).
+// ldo is a multiple of 64, so every array is 8-aligned.
+struct MassItemOut {
+    double *mass, *energy, *dmin, *sz;
+    int64_t *points, *nodes;
+    int32_t* status;
+};
+inline size_t mass_out_bytes(int d, int64_t ldo, bool moments) {
+    return (size_t)ldo * (44 + (moments ? (size_t)d * 8 : 0));
+}
+inline MassItemOut mass_out_at(void* p, int64_t ldo, bool moments) {
+    MassItemOut o;
+    o.mass = (double*)p;
+    o.energy = o.mass + ldo;
+    o.dmin = o.energy + ldo;
+    o.points = (int64_t*)(o.dmin + ldo);
+    o.nodes = o.points + ldo;
+    o.status = (int32_t*)(o.nodes + ldo);
+    o.sz = moments ? (double*)(o.status + ldo) : nullptr;
+    return o;
+}
 struct MassArgs {
     int d;
     int top;             // the level the items hang from (d: whole trees)

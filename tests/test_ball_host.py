@@ -143,9 +143,11 @@ def test_libraries_export_the_symbols():
 
 def test_product_library_reads_no_environment():
     src = open(os.path.join(CSRC, "lgs_capi.hip")).read()
-    body = src[src.index("int ball_run("):src.index("int ball_outputs(")]
+    body = src[src.index("EnumTuning enum_tuning("):]
+    body = body[:body.index("\n}\n")]
     for h in ("LGS_TEST_MASS_SPLIT", "LGS_TEST_CVP_SLICE", "LGS_TEST_CVP_SLOTS"):
         assert f'hook("{h}")' in body
+        assert src.count(h) == 1  # (the tuning is read in one place, by every enumeration)
     assert "getenv(" not in body
     txt = open(os.path.join(CSRC, "lgs_exact.hip")).read()
     assert "getenv" not in txt and "printf" not in txt and "assert(" not in txt and "asm" not in txt

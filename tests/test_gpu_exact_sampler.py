@@ -187,6 +187,47 @@ def test_single_centre_split_over_calls_and_device_pointers(capi, setups, oracle
     assert np.array_equal(ix.cpu().numpy(), whole["index"]) and np.array_equal(d2.cpu().numpy(), whole["dist2"])
 
 
+def test_table_over_several_chunks(capi, setups):
+    """lgs_exact_table over three chunks of targets (d2, 130 targets, max_proposals = 64): the
+    listing pass writes into the context's table with recomputed centres.  Host and device
+    pointers; everything equals the one-chunk table of a default context, byte for byte."""
+    import torch
+    s = setups["d2"]
+    sigma, n = 0.8, 130
+    T = np.array(s["T"][:n])  # (a writable copy: it also goes to the device through torch)
+    cv = _context(capi, s).closest_vector_host(T, 1 << 20, want_z=False, want_v=False)
+    assert not cv["status"].any()
+    shift = cv["dist2"].copy()
+    r2 = shift + 2.0 * sigma * sigma * NATS
+    one = _context(capi, s)
+    want = one.exact_table_host(T, sigma, r2, shift, MAX_NODES, want_weights=True)
+    total = int(want["offsets"][n])
+    assert not want["status"].any() and total >= 2 * n
+    seed, first = 31, (1 << 32) - 100
+    draws = one.exact_sample_host(seed, first, 3, n)
+
+    def check(ctx, got):
+        for k in ("offsets", "nodes", "status", "mass", "weights", "cum"):
+            assert got[k].dtype == want[k].dtype and got[k].tobytes() == want[k].tobytes(), k
+        r = ctx.exact_sample_host(seed, first, 3, n)
+        for k in ("z", "index", "dist2"):
+            assert r[k].dtype == draws[k].dtype and r[k].tobytes() == draws[k].tobytes(), k
+
+    host = _context(capi, s, max_proposals=64)
+    check(host, host.exact_table_host(T, sigma, r2, shift, MAX_NODES, want_weights=True))
+    dev = dict(device="cuda:0")
+    out = dict(offsets=torch.full((n + 1,), -1, dtype=torch.int64, **dev),
+               nodes=torch.full((n,), -1, dtype=torch.int64, **dev),
+               status=torch.full((n,), -1, dtype=torch.int32, **dev),
+               mass=torch.zeros(n, dtype=torch.float64, **dev),
+               weights=torch.zeros(total, dtype=torch.float64, **dev),
+               cum=torch.zeros(total, dtype=torch.float64, **dev))
+    device = _context(capi, s, max_proposals=64)
+    device.exact_table(torch.as_tensor(T, **dev), sigma, torch.as_tensor(r2, **dev), torch.as_tensor(shift, **dev),
+                       MAX_NODES, total, flags=capi.LGS_DEVICE_PTRS, **out)
+    check(device, {k: v.cpu().numpy() for k, v in out.items()})
+
+
 # ------------------------------------------------------------------ 3. statistics
 def _d2_exact_pmf(B, sigma, t, half=12):
     """D_{Lambda,sigma,t} over coefficients z in [-half, half]^2, by enumeration (the host box
