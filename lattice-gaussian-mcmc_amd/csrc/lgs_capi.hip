@@ -233,7 +233,7 @@ struct lgs_ctx {
     // their weights and running sums, the targets' row and block offsets, the block totals and
     // prefixes, the masses (lgs_set_basis discards it)
     DevBuf TBL_Z, TBL_D, TBL_W, TBL_S, TBL_OFF, TBL_BOFF, TBL_BTOT, TBL_BPRE, TBL_M;
-    // lgs_lll_reduce: the chunk's state blocks, the two live lists, the live counter and range
+    // lgs_lll_reduce and lgs_bkz_reduce: the chunk's state blocks, the two live lists, the live counter and range
     // flag, and (host pointers) the chunk's inputs and outputs
     DevBuf LLL_ST, LLL_LIVE[2], LLL_CTL, LLL_IO;
     bool has_table = false;
@@ -3948,6 +3948,141 @@ int lgs_lll_reduce(lgs_ctx* c, int64_t n, int64_t d, const int64_t* basis, doubl
             HIP_TRY(back(o.swaps ? o.swaps + off : nullptr, a.swaps, (size_t)m * 8));
             HIP_TRY(back(o.iters ? o.iters + off : nullptr, a.iters, (size_t)m * 8));
             HIP_TRY(back(o.passes ? o.passes + off : nullptr, a.passes, (size_t)m * 8));
+            HIP_TRY(back(o.status ? o.status + off : nullptr, a.status, (size_t)m * 4));
+            HIP_TRY(back(o.gs_norm2 ? o.gs_norm2 + (size_t)off * d : nullptr, a.gs_norm2, (size_t)m * d * 8));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+        fold_timers(c);
+    }
+    return LGS_OK;
+}
+
+// BKZ reduction of n bases (lgs_bkz.hip), in the pattern of lgs_lll_reduce above and
+// on its buffers: per chunk the zeroed state blocks, the LLL image from the caller's bases
+// (lll_init, at the longer pitch), the range flag, then launches of at most `slice` LLL
+// iterations and `nslice` enumeration nodes per basis until the live list is empty.
+int lgs_bkz_reduce(lgs_ctx* c, int64_t n, int64_t d, const int64_t* basis, int64_t block_size, double delta,
+                   double eta, int64_t max_tours, int64_t max_iters, int64_t enum_nodes, int64_t* basis_out,
+                   int64_t* U_out, const lgs_bkz_outputs* out, uint32_t flags) {
+    if (!c) return fail(LGS_ERR_INVALID, "null context");
+    if (flags & ~(uint32_t)LGS_DEVICE_PTRS) return fail(LGS_ERR_INVALID, "lgs_bkz_reduce: unsupported flags 0x%x", flags);
+    if (d < 2 || d > LGS_LLL_MAX_D)
+        return fail(LGS_ERR_INVALID, "lgs_bkz_reduce: d = %lld outside 2..LGS_LLL_MAX_D (%d)", (long long)d,
+                    LGS_LLL_MAX_D);
+    if (block_size < 2 || block_size > LGS_BKZ_MAX_BLOCK)
+        return fail(LGS_ERR_INVALID, "lgs_bkz_reduce: block_size = %lld outside 2..LGS_BKZ_MAX_BLOCK (%d)",
+                    (long long)block_size, LGS_BKZ_MAX_BLOCK);
+    if (!(delta > 0.25 && delta < 1.0)) return fail(LGS_ERR_INVALID, "delta must lie in (0.25, 1)");
+    if (!(eta > 0.5 && eta < 1.0)) return fail(LGS_ERR_INVALID, "eta must lie in (0.5, 1)");
+    const int64_t cap = (int64_t)1 << 40;
+    if (max_tours < 1 || max_tours > cap) return fail(LGS_ERR_INVALID, "max_tours must be 1..2^40");
+    if (max_iters < 1 || max_iters > cap) return fail(LGS_ERR_INVALID, "max_iters must be 1..2^40");
+    if (enum_nodes < 1 || enum_nodes > cap) return fail(LGS_ERR_INVALID, "enum_nodes must be 1..2^40");
+    if (n < 0) return fail(LGS_ERR_INVALID, "n < 0");
+    if (n == 0) return LGS_OK;
+    if (!basis || !basis_out || !U_out) return fail(LGS_ERR_INVALID, "basis, basis_out and U_out are required");
+    const bool dev = (flags & LGS_DEVICE_PTRS) != 0;
+    const size_t dd = (size_t)d * (size_t)d;
+    if (!dev)
+        for (size_t k = 0; k < (size_t)n * dd; ++k)
+            if (basis[k] >= lgs::kLllMaxB || basis[k] <= -lgs::kLllMaxB)
+                return fail(LGS_ERR_INVALID, "basis %lld: an |entry| >= 2^28", (long long)(k / dd));
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    const lgs_bkz_outputs none{};
+    const lgs_bkz_outputs& o = out ? *out : none;
+    int64_t slice = lgs::kLllSlice, nslice = lgs::kBkzNodeSlice;
+    // (hooks build) LGS_TEST_LLL_SLICE / LGS_TEST_BKZ_SLICE: LLL iterations and enumeration nodes per
+    // basis and launch -- tests suspend every LLL and every enumeration
+    if (const char* s = hook("LGS_TEST_LLL_SLICE")) slice = std::max<int64_t>(1, atoll(s));
+    if (const char* s = hook("LGS_TEST_BKZ_SLICE")) nslice = std::max<int64_t>(1, atoll(s));
+    const int64_t chunk = std::min<int64_t>(n, lgs::kLllChunk);
+    const size_t words = lgs::bkz_state_words((int)d);
+    // LLL_IO (host pointers): basis | basis_out | U_out | the eight int64 counters | gs_norm2 | status
+    const size_t io_b = (size_t)chunk * dd * 8, io_s = (size_t)chunk * 8, io_g = (size_t)chunk * d * 8;
+    if ((rc = c->LLL_ST.reserve((size_t)chunk * words * 8)) || (rc = c->LLL_LIVE[0].reserve((size_t)chunk * 4)) ||
+        (rc = c->LLL_LIVE[1].reserve((size_t)chunk * 4)) || (rc = c->LLL_CTL.reserve(16)) ||
+        (!dev && (rc = c->LLL_IO.reserve(3 * io_b + 8 * io_s + io_g + (size_t)chunk * 4))))
+        return rc;
+    char* io = c->LLL_IO.as<char>();
+    int64_t* const host_ctr[8] = {o.swaps, o.iters, o.passes, o.tours, o.blocks, o.insertions, o.nodes, o.truncated};
+    for (int64_t off = 0; off < n; off += chunk) {
+        const int64_t m = std::min<int64_t>(chunk, n - off);
+        lgs::BkzArgs b{};
+        lgs::LllArgs& a = b.l;
+        a.d = (int)d;
+        a.m = m;
+        a.slice = slice;
+        a.max_iters = max_iters;
+        a.delta = delta;
+        a.eta = eta;
+        a.state = c->LLL_ST.as<int64_t>();
+        a.state_words = words;
+        a.ctl = c->LLL_CTL.as<unsigned long long>();
+        a.flags = (unsigned int*)(a.ctl + 1);
+        b.block_size = (int)block_size;
+        b.max_tours = max_tours;
+        b.enum_nodes = enum_nodes;
+        b.node_slice = nslice;
+        int64_t** const ctr[8] = {&a.swaps, &a.iters, &a.passes, &b.tours, &b.blocks, &b.insertions, &b.nodes, &b.truncated};
+        if (dev) {
+            a.basis = basis + (size_t)off * dd;
+            a.basis_out = basis_out + (size_t)off * dd;
+            a.U_out = U_out + (size_t)off * dd;
+            for (int f = 0; f < 8; ++f) *ctr[f] = host_ctr[f] ? host_ctr[f] + off : nullptr;
+            a.status = o.status ? o.status + off : nullptr;
+            a.gs_norm2 = o.gs_norm2 ? o.gs_norm2 + (size_t)off * d : nullptr;
+        } else {
+            a.basis = (const int64_t*)io;
+            a.basis_out = (int64_t*)(io + io_b);
+            a.U_out = (int64_t*)(io + 2 * io_b);
+            for (int f = 0; f < 8; ++f) *ctr[f] = (int64_t*)(io + 3 * io_b + f * io_s);
+            a.gs_norm2 = (double*)(io + 3 * io_b + 8 * io_s);
+            a.status = (int32_t*)(io + 3 * io_b + 8 * io_s + io_g);
+            HIP_TRY(hipMemcpyAsync(io, basis + (size_t)off * dd, (size_t)m * dd * 8, hipMemcpyHostToDevice, c->stream));
+        }
+        HIP_TRY(hipMemsetAsync(a.ctl, 0, 16, c->stream));
+        HIP_TRY(hipMemsetAsync(a.state, 0, (size_t)m * words * 8, c->stream));
+        {
+            Scope s(c, 9);
+            HIP_TRY(lgs::launch::lll_init(a, c->stream));
+        }
+        unsigned long long cv[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(cv, a.ctl, 16, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if ((unsigned int)cv[1] & lgs::kLllFlagRange) {
+            fold_timers(c);
+            return fail(LGS_ERR_INVALID, "bases %lld..%lld: an |entry| >= 2^28", (long long)off, (long long)(off + m - 1));
+        }
+        // a launch that suspends a basis has spent a whole slice of it: of the LLL iterations, of
+        // which the call has max_iters, or of the nodes, at most enum_nodes in each of d - 1 blocks a tour
+        const double bound = std::ceil((double)max_iters / (double)slice) +
+                             std::ceil((double)max_tours * (double)(d - 1) * (double)enum_nodes / (double)nslice) + 2.0;
+        int64_t live = m;
+        int cur = 0;
+        for (double launches = 0.0; live > 0; launches += 1.0) {
+            if (launches > bound) return fail(LGS_ERR_HIP, "lgs_bkz_reduce: launch bound exceeded (a library bug)");
+            a.nlive = live;
+            a.live_in = launches == 0.0 ? nullptr : c->LLL_LIVE[cur ^ 1].as<int32_t>();
+            a.live_out = c->LLL_LIVE[cur].as<int32_t>();
+            HIP_TRY(hipMemsetAsync(a.ctl, 0, 8, c->stream));
+            {
+                Scope s(c, 9);
+                HIP_TRY(lgs::launch::bkz_reduce(b, c->stream));
+            }
+            HIP_TRY(hipMemcpyAsync(cv, a.ctl, 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (cv[0] > (unsigned long long)live) return fail(LGS_ERR_HIP, "lgs_bkz_reduce: live count (a library bug)");
+            live = (int64_t)cv[0];
+            cur ^= 1;
+        }
+        if (!dev) {
+            const auto back = [&](void* dst, const void* src, size_t bytes) {
+                return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+            };
+            HIP_TRY(back(basis_out + (size_t)off * dd, a.basis_out, (size_t)m * dd * 8));
+            HIP_TRY(back(U_out + (size_t)off * dd, a.U_out, (size_t)m * dd * 8));
+            for (int f = 0; f < 8; ++f) HIP_TRY(back(host_ctr[f] ? host_ctr[f] + off : nullptr, *ctr[f], (size_t)m * 8));
             HIP_TRY(back(o.status ? o.status + off : nullptr, a.status, (size_t)m * 4));
             HIP_TRY(back(o.gs_norm2 ? o.gs_norm2 + (size_t)off * d : nullptr, a.gs_norm2, (size_t)m * d * 8));
             HIP_TRY(hipStreamSynchronize(c->stream));

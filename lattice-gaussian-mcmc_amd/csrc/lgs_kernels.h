@@ -332,6 +332,7 @@ struct LllArgs {
     int64_t max_iters;
     double delta, eta;
     int64_t* state;      // m state blocks of lll_state_words(d) words
+    size_t state_words;  // (lll_init) the pitch of the state blocks when it is not that: lgs_bkz_reduce's
     const int64_t* basis;  // m x d x d row-major, vector i in column i (lll_init only)
     int64_t* basis_out;  // m x d x d
     int64_t* U_out;      // m x d x d
@@ -341,6 +342,42 @@ struct LllArgs {
     int32_t* status;
     double* gs_norm2;    // m x d
     unsigned int* flags;  // one word: kLllFlagRange
+};
+
+// ---- BKZ basis reduction (lgs_bkz.hip, lgs_bkz_reduce)
+// One basis per block of one wave, on the LLL image above extended by the state of the tour and
+// of the block enumeration in work; as there, the state block in device memory is the LDS image:
+//   LLL image        lll_state_words(d) words
+//   header           kBkzHdr words: phase, kb, tours, ins, blocks, insertions, nodes, truncated,
+//                    nodes_b, level i, top (both relative to kb), A (fp64), best exists
+//   x | c | P | stp | nxt   kBkzLanes words each, fp64: lane l owns level kb + l; x, stp and nxt
+//                    hold integers (exact in fp64), P is P[kb + l + 1], the distance above the level
+//   S                kBkzMaxBlock x (kBkzMaxBlock + 1) fp64: S[l][j] the partial centre sum of
+//                    level kb + l over the levels kb + j .. e (row pitch odd: a lane owns a row)
+//   best             kBkzMaxBlock words, fp64: x[kb .. e] of the shortest vector found
+// A launch advances a basis by at most `slice` LLL iterations and `node_slice` enumeration nodes.
+constexpr int kBkzMaxBlock = 32;  // LGS_BKZ_MAX_BLOCK
+constexpr int kBkzHdr = 16;
+constexpr int kBkzLanes = 64;
+constexpr int kBkzSPitch = kBkzMaxBlock + 1;
+constexpr int64_t kBkzNodeSlice = 1 << 16;  // enumeration nodes of a basis per launch at most
+constexpr int kBkzExtWords = kBkzHdr + 5 * kBkzLanes + kBkzMaxBlock * kBkzSPitch + kBkzMaxBlock;
+__host__ __device__ inline size_t bkz_state_words(int d) { return lll_state_words(d) + kBkzExtWords; }
+inline size_t bkz_lds_bytes(int d) { return bkz_state_words(d) * 8; }  // 145 088 B at d = 64
+// what BKZ adds fits beside the largest LLL image in the 160 KiB of a CU
+static_assert(kBkzExtWords * 8 <= 160 * 1024 - (4 * kLllMaxD * (kLllMaxD | 1) + kLllLanes + kLllHdr) * 8,
+              "the BKZ state does not fit in LDS");
+static_assert(kBkzExtWords * 8 <= 30144, "the BKZ state exceeds the LDS the LLL image leaves at d = 64");
+struct BkzArgs {
+    LllArgs l;            // state: m blocks of bkz_state_words(d) words; l.slice, l.max_iters, outputs
+    int block_size;
+    int64_t max_tours, enum_nodes;
+    int64_t node_slice;   // enumeration nodes per basis and launch
+    int64_t* tours;       // m (each of the five nullable)
+    int64_t* blocks;
+    int64_t* insertions;
+    int64_t* nodes;
+    int64_t* truncated;
 };
 
 // ---- exact Gaussian mass: fixed-radius enumeration (lgs_cvp.hip, lgs_gaussian_mass)
@@ -733,6 +770,9 @@ hipError_t mass_compact(const MassState& src, const MassState& dst, int64_t S, c
 // over the a.nlive bases of a.live_in.
 hipError_t lll_init(const LllArgs& a, hipStream_t st);
 hipError_t lll_reduce(const LllArgs& a, hipStream_t st);
+// ---- BKZ basis reduction (lgs_bkz.hip): one launch over the a.l.nlive bases of a.l.live_in; the
+// state blocks come from lll_init with state_words = bkz_state_words(d), the rest zeroed.
+hipError_t bkz_reduce(const BkzArgs& a, hipStream_t st);
 // The exact sampler's table (lgs_exact.hip): w and the blocked running sum of every row, in
 // three launches -- weights and c_m per block, P_b and M per target, S_m = P_b + c_m -- and
 // the draws of one chunk (tb / ob: the element widths of the table's rows and of a.W).

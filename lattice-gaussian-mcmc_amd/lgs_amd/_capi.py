@@ -59,6 +59,7 @@ LGS_CVP_MAX_D = 64
 LGS_MASS_MAX_D = 64          # lgs_gaussian_mass
 LGS_MASS_MOMENTS_MAX_D = 40  # ... with sum_z
 LGS_LLL_MAX_D = 64           # lgs_lll_reduce (its launches are timer KERNEL_CVP_ENUM too)
+LGS_BKZ_MAX_BLOCK = 32       # lgs_bkz_reduce (timer KERNEL_CVP_ENUM as well)
 LGS_COUNTER_RESOLVED = 0
 LGS_COUNTER_FALLBACK = 1
 LGS_COUNTER_ACCEPT_RESOLVED = 2
@@ -79,7 +80,7 @@ EXPORTS = ("lgs_version", "lgs_last_error", "lgs_create", "lgs_create_ex", "lgs_
            "lgs_jump_distance", "lgs_marginal_tvd", "lgs_column_range", "lgs_histogram", "lgs_set_decoder", "lgs_nearest_plane",
            "lgs_round_decode", "lgs_counter", "lgs_qskip_elided", "lgs_klein_targets", "lgs_klein_decode",
            "lgs_imhk_targets", "lgs_closest_vector", "lgs_gaussian_mass", "lgs_ball_points", "lgs_exact_table",
-           "lgs_exact_sample", "lgs_lll_reduce")
+           "lgs_exact_sample", "lgs_lll_reduce", "lgs_bkz_reduce")
 
 
 class ImhkOutputs(ctypes.Structure):
@@ -135,6 +136,14 @@ class LllOutputs(ctypes.Structure):
     """struct lgs_lll_outputs (include/lgs.h)."""
     _fields_ = [("swaps", ctypes.c_void_p), ("iters", ctypes.c_void_p), ("passes", ctypes.c_void_p),
                 ("status", ctypes.c_void_p), ("gs_norm2", ctypes.c_void_p)]
+
+
+class BkzOutputs(ctypes.Structure):
+    """struct lgs_bkz_outputs (include/lgs.h)."""
+    _fields_ = [("swaps", ctypes.c_void_p), ("iters", ctypes.c_void_p), ("passes", ctypes.c_void_p),
+                ("tours", ctypes.c_void_p), ("blocks", ctypes.c_void_p), ("insertions", ctypes.c_void_p),
+                ("nodes", ctypes.c_void_p), ("truncated", ctypes.c_void_p), ("status", ctypes.c_void_p),
+                ("gs_norm2", ctypes.c_void_p)]
 
 
 class LgsError(RuntimeError):
@@ -235,6 +244,9 @@ def load_library(path: str = LIB_PATH):
     if hasattr(L, "lgs_lll_reduce"):  # (older A/B baselines lack it)
         L.lgs_lll_reduce.argtypes = [_vp, _i64, _i64, _vp, ctypes.c_double, ctypes.c_double, _i64, _vp, _vp,
                                      ctypes.POINTER(LllOutputs), ctypes.c_uint32]
+    if hasattr(L, "lgs_bkz_reduce"):  # (older A/B baselines lack it)
+        L.lgs_bkz_reduce.argtypes = [_vp, _i64, _i64, _vp, _i64, ctypes.c_double, ctypes.c_double, _i64, _i64, _i64,
+                                     _vp, _vp, ctypes.POINTER(BkzOutputs), ctypes.c_uint32]
     for name in EXPORTS:
         if name not in ("lgs_version", "lgs_last_error") and hasattr(L, name):
             getattr(L, name).restype = ctypes.c_int
@@ -1031,6 +1043,60 @@ class Context:
                "gs_norm2": np.empty((n, d))}
         self.lll_reduce(b, out["basis"], out["U"], delta, eta, max_iters, out["swaps"], out["iters"], out["passes"],
                         out["status"], out["gs_norm2"])
+        return out
+
+    # ---------------------------------------------------------------- BKZ reduction
+    _BKZ_COUNTERS = ("swaps", "iters", "passes", "tours", "blocks", "insertions", "nodes", "truncated")
+
+    @classmethod
+    def _bkz_args(cls, basis, block_size, delta, eta, max_tours, max_iters, enum_nodes, flags):
+        """Argument checks of bkz_reduce / bkz_reduce_host, before any library call; returns (n, d)."""
+        if isinstance(flags, bool) or not isinstance(flags, (int, np.integer)) or flags & ~LGS_DEVICE_PTRS:
+            raise ValueError(f"bkz_reduce: unsupported flags {flags!r}")
+        n, d = cls._lll_args(basis, delta, eta, max_iters, flags)
+        for name, v, lo, hi in (("block_size", block_size, 2, LGS_BKZ_MAX_BLOCK), ("max_tours", max_tours, 1, 1 << 40),
+                                ("enum_nodes", enum_nodes, 1, 1 << 40)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+                raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
+        return n, d
+
+    def bkz_reduce(self, basis, basis_out, U_out, block_size, delta=0.99, eta=0.51, max_tours=1 << 40,
+                   max_iters=1 << 40, enum_nodes=1 << 40, swaps=None, iters=None, passes=None, tours=None,
+                   blocks=None, insertions=None, nodes=None, truncated=None, status=None, gs_norm2=None, flags=0):
+        """Raw lgs_bkz_reduce on caller buffers (numpy host arrays, or device tensors with
+        LGS_DEVICE_PTRS): basis, basis_out, U_out (n, d, d) int64 with vector i in COLUMN i
+        (basis_out = basis @ U_out); the eight counters (n,) int64, status (n,) int32, gs_norm2
+        (n, d) float64, all optional.  Needs no loaded basis."""
+        n, d = self._bkz_args(basis, block_size, delta, eta, max_tours, max_iters, enum_nodes, flags)
+        ctr = (swaps, iters, passes, tours, blocks, insertions, nodes, truncated)
+        _check_bufs(flags, self.device, ((basis, "int64", "basis"), (basis_out, "int64", "basis_out"),
+                                         (U_out, "int64", "U_out"), (status, "int32", "status"),
+                                         (gs_norm2, "float64", "gs_norm2")) +
+                    tuple((b, "int64", nm) for b, nm in zip(ctr, self._BKZ_COUNTERS)))
+        if basis_out is None or U_out is None:
+            raise ValueError("basis_out and U_out are required")
+        self._check_shapes(((basis_out, (n, d, d), "basis_out"), (U_out, (n, d, d), "U_out"), (status, (n,), "status"),
+                            (gs_norm2, (n, d), "gs_norm2")) +
+                           tuple((b, (n,), nm) for b, nm in zip(ctr, self._BKZ_COUNTERS)))
+        self._ck(self._L.lgs_bkz_reduce(self._h, n, d, _ptr(basis), int(block_size), float(delta), float(eta),
+                                        int(max_tours), int(max_iters), int(enum_nodes), _ptr(basis_out), _ptr(U_out),
+                                        _outputs(BkzOutputs, *ctr, status, gs_norm2), int(flags)))
+
+    def bkz_reduce_host(self, basis, block_size, delta=0.99, eta=0.51, max_tours=1 << 40, max_iters=1 << 40,
+                        enum_nodes=1 << 40):
+        """BKZ of host bases (n, d, d) int64, vectors in columns, into fresh host arrays {"basis",
+        "U", the eight counters, "status", "gs_norm2"}."""
+        b = np.ascontiguousarray(basis)
+        if b.dtype != np.int64:
+            raise ValueError(f"basis: expected int64, got {b.dtype}")
+        n, d = self._bkz_args(b, block_size, delta, eta, max_tours, max_iters, enum_nodes, 0)
+        if np.any(np.abs(b) >= 1 << 28):
+            raise ValueError("basis entries must be below 2^28 in magnitude")
+        out = {"basis": np.empty((n, d, d), dtype=np.int64), "U": np.empty((n, d, d), dtype=np.int64),
+               "status": np.empty(n, dtype=np.int32), "gs_norm2": np.empty((n, d))}
+        out.update({nm: np.empty(n, dtype=np.int64) for nm in self._BKZ_COUNTERS})
+        self.bkz_reduce(b, out["basis"], out["U"], block_size, delta, eta, max_tours, max_iters, enum_nodes,
+                        *(out[nm] for nm in self._BKZ_COUNTERS), out["status"], out["gs_norm2"])
         return out
 
     # ---------------------------------------------------------------- diagnostics

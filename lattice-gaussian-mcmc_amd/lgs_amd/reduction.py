@@ -1,10 +1,14 @@
-"""LLL basis reduction on the GPU (``lgs_lll_reduce``).
+"""LLL and BKZ basis reduction on the GPU (``lgs_lll_reduce``, ``lgs_bkz_reduce``).
 
 The enumeration entry points (``closest_vector``, ``gaussian_mass``, ``ball_points``, the exact
 sampler) stop at a node budget, and on the raw q-ary / NTRU bases of ``lgs_amd.lattices`` that
 budget is what they hit: their shortest row is as long as q.  ``lll_reduce`` is the remedy the
 reference takes from Sage (``src/lattices/reduction.py:68-186``), here one wave per basis and
 whole batches per call, with the transformation returned as exact integers.
+
+``bkz_reduce`` goes on where LLL stops (``src/lattices/reduction.py:238-318``): the Gram-Schmidt
+profile, which sets the size of those trees and the smallest sigma at which Klein and IMHK are
+close to their target, improves only with block reduction.
 
 ``LatticeReduction`` restates the reference's host-side quality measures (Hermite factor,
 orthogonality defect, Gram-Schmidt profile) in NumPy around that reduction.
@@ -73,6 +77,37 @@ def lll_reduce(basis, delta: float = 0.99, eta: float = 0.51, max_iters: int = 1
     return red, U, info
 
 
+_BKZ_INFO = ("swaps", "iters", "passes", "tours", "blocks", "insertions", "nodes", "truncated", "status", "gs_norm2")
+
+
+def bkz_reduce(basis, block_size: int, delta: float = 0.99, eta: float = 0.51, max_tours: int = 1024,
+               enum_nodes: int = 1 << 30, max_iters: int = 1 << 40, rows: bool = True, device: int = 0):
+    """BKZ-reduce one (d, d) basis or a batch (n, d, d) of integral bases, 2 <= d <= 64, with
+    blocks of ``block_size`` (2..32) vectors.
+
+    Conventions and the shape of the result are ``lll_reduce``'s: ``(reduced, U, info)`` with
+    ``reduced = U @ basis`` for ``rows=True``.  ``info`` holds the LLL counters summed over the
+    call, ``tours``, ``blocks``, ``insertions``, ``nodes``, ``truncated`` (block enumerations cut
+    at ``enum_nodes`` nodes), ``gs_norm2`` and ``status``: 0 = a whole tour made no insertion,
+    1 = ``max_iters`` reached, 2 = a magnitude guard stopped the reduction, 3 = the input is not
+    a basis, 4 = ``max_tours`` tours done.  Status 0 means BKZ-reduced only with ``truncated == 0``.
+    With any status the result is a basis of the same lattice and ``U`` is consistent with it."""
+    b = _integral(basis)
+    single = b.ndim == 2
+    if b.ndim not in (2, 3) or b.shape[-1] != b.shape[-2]:
+        raise ValueError(f"basis must have shape (d, d) or (n, d, d), got {b.shape}")
+    b3 = b[None] if single else b
+    cols = np.ascontiguousarray(np.swapaxes(b3, 1, 2) if rows else b3)
+    r = _context(device).bkz_reduce_host(cols, block_size, delta, eta, max_tours, max_iters, enum_nodes)
+    red, U = r["basis"], r["U"]
+    if rows:
+        red, U = np.ascontiguousarray(np.swapaxes(red, 1, 2)), np.ascontiguousarray(np.swapaxes(U, 1, 2))
+    info = {k: r[k] for k in _BKZ_INFO}
+    if single:
+        return red[0], U[0], {k: (v[0] if v.ndim > 1 else v[0].item()) for k, v in info.items()}
+    return red, U, info
+
+
 def _gs_norms(B):
     """Gram-Schmidt norms of the rows of B (float64)."""
     return np.abs(np.diag(np.linalg.qr(np.asarray(B, dtype=np.float64).T, mode="r")))
@@ -101,6 +136,49 @@ class LatticeReduction:
         diag = {"time": dt, "initial_quality": before, "final_quality": after,
                 "improvement_factor": before["hermite_factor"] / after["hermite_factor"], "delta": delta,
                 "lll": info}
+        self.stats["reductions_performed"] += 1
+        self.stats["total_time"] += dt
+        self.stats["quality_improvements"].append(diag["improvement_factor"])
+        return red.astype(np.float64), U.astype(np.float64), diag
+
+    @staticmethod
+    def _progressive_block_sizes(n: int, target: int):
+        """min(20, n), +10, ..., target (``reduction.py:302-312``)."""
+        sizes, beta = [], min(20, n)
+        while beta < target:
+            sizes.append(beta)
+            beta = min(beta + 10, target)
+        sizes.append(target)
+        return sizes
+
+    def bkz_reduce(self, basis, block_size: int, strategy: str = "default", progressive: bool = False):
+        """(reduced, U, diagnostics) with reduced = U @ basis (``reduction.py:238-300``);
+        diagnostics holds the reference's keys -- time, block_size, block_sizes_used, strategy,
+        initial_quality, final_quality, improvement_factor -- and the counters of every run under
+        ``bkz``.  ``progressive`` runs the block sizes min(20, n), +10, ..., block_size in turn,
+        each capped at 32, and composes the transformations exactly.  Only the default strategy
+        exists; a run that does not end with status 0, or that cut an enumeration short, raises."""
+        if strategy != "default":
+            raise ValueError(f"bkz_reduce: unknown strategy {strategy!r} (only 'default')")
+        t0 = time.time()
+        before = self.basis_quality_profile(basis)
+        n = np.asarray(basis).shape[0]
+        sizes = self._progressive_block_sizes(n, block_size) if progressive else [block_size]
+        sizes = [min(int(b), _capi.LGS_BKZ_MAX_BLOCK) for b in sizes]
+        red, U, runs = basis, None, []
+        for beta in sizes:
+            red, Ub, info = bkz_reduce(red, beta, rows=True, device=self.device)
+            if np.any(np.asarray(info["status"]) != 0) or np.any(np.asarray(info["truncated"]) != 0):
+                raise RuntimeError(f"BKZ-{beta} did not finish: status {info['status']}, "
+                                   f"truncated {info['truncated']}")
+            # python ints: the product of two transformations may pass 2^63 where each fits
+            U = Ub if U is None else np.array(Ub.astype(object) @ U.astype(object), dtype=np.int64)
+            runs.append(info)
+        after = self.basis_quality_profile(red)
+        dt = time.time() - t0
+        diag = {"time": dt, "block_size": block_size, "block_sizes_used": sizes, "strategy": strategy,
+                "initial_quality": before, "final_quality": after,
+                "improvement_factor": before["hermite_factor"] / after["hermite_factor"], "bkz": runs}
         self.stats["reductions_performed"] += 1
         self.stats["total_time"] += dt
         self.stats["quality_improvements"].append(diag["improvement_factor"])
