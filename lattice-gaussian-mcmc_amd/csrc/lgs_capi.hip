@@ -236,6 +236,9 @@ struct lgs_ctx {
     // lgs_lll_reduce and lgs_bkz_reduce: the chunk's state blocks, the two live lists, the live counter and range
     // flag, and (host pointers) the chunk's inputs and outputs
     DevBuf LLL_ST, LLL_LIVE[2], LLL_CTL, LLL_IO;
+    // lgs_closest_vector_bases: the chunk's workspace (factors, centres, search state, staged
+    // inputs and outputs) and the two live lists (its live counter and flag word: CVP_CTL)
+    DevBuf CVPB_WS, CVPB_LIVE[2];
     bool has_table = false;
     int64_t tbl_n = 0, tbl_rows = 0;
     int tbl_zb = 4;
@@ -3589,6 +3592,183 @@ int lgs_closest_vector(lgs_ctx* c, int64_t n, const double* targets, const doubl
         if ((rc = finish(c))) return rc;
     }
     return finish(c);
+}
+
+// Exact closest vectors over a batch of bases (lgs_cvpb.hip).  The inputs are
+// checked first (host buffers here, device buffers by cvpb_check); then, per chunk of `slots`
+// bases: the QR of every basis with its targets (timer 7), enumeration launches of at most
+// `slice` nodes per problem over the bases of the live list -- written by each launch, read by
+// the next -- until it is empty (timer 9), and the problems' outputs into the workspace (timer
+// 8).  The chunk's outputs reach the caller only after its flag word came back clean.  No
+// loaded basis is read or touched; the flag word is the call's own (CVP_CTL).
+int lgs_closest_vector_bases(lgs_ctx* c, int64_t n_bases, int64_t d, int64_t T, const double* bases,
+                             const double* targets, const double* radius2, int64_t max_nodes, void* z_out,
+                             double* v_out, const lgs_cvp_bases_outputs* out, uint32_t flags) {
+    const char* const fn = "lgs_closest_vector_bases";
+    if (!c) return fail(LGS_ERR_INVALID, "null context");
+    if (flags & ~(uint32_t)(LGS_DEVICE_PTRS | LGS_Z64)) return fail(LGS_ERR_INVALID, "%s: unsupported flags 0x%x", fn, flags);
+    if (d < 2 || d > LGS_CVP_MAX_D)
+        return fail(LGS_ERR_INVALID, "%s: d = %lld outside 2..LGS_CVP_MAX_D (%d)", fn, (long long)d, LGS_CVP_MAX_D);
+    if (T < 1 || T > LGS_CVPB_MAX_T)
+        return fail(LGS_ERR_INVALID, "%s: T = %lld outside 1..LGS_CVPB_MAX_T (%d)", fn, (long long)T, LGS_CVPB_MAX_T);
+    int rc = check_max_nodes(max_nodes);
+    if (rc) return rc;
+    if (n_bases < 0) return fail(LGS_ERR_INVALID, "n_bases < 0");
+    if (n_bases == 0) return LGS_OK;
+    if (!bases || !targets) return fail(LGS_ERR_INVALID, "bases and targets are required");
+    if ((rc = check_ctx(c, false))) return rc;
+    const bool dev = (flags & LGS_DEVICE_PTRS) != 0;
+    const int ob = (flags & LGS_Z64) ? 8 : 4;
+    const size_t dd = (size_t)d * d, td = (size_t)T * d;
+    if ((rc = c->CVP_CTL.reserve(16))) return rc;
+    unsigned long long* ctl = c->CVP_CTL.as<unsigned long long>();
+    unsigned int* fl = (unsigned int*)(ctl + 1);
+    unsigned long long cv[2] = {0, 0};
+    std::vector<double> rh;
+    if (dev) {
+        HIP_TRY(hipMemsetAsync(ctl, 0, 16, c->stream));
+        {
+            Scope s(c, 7);
+            HIP_TRY(lgs::launch::cvpb_check(bases, (int64_t)((size_t)n_bases * dd), fl, c->stream));
+            HIP_TRY(lgs::launch::cvpb_check(targets, (int64_t)((size_t)n_bases * td), fl, c->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(cv, ctl, 16, hipMemcpyDeviceToHost, c->stream));
+        if (radius2) {
+            rh.resize((size_t)n_bases * T);
+            HIP_TRY(hipMemcpyAsync(rh.data(), radius2, rh.size() * 8, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        fold_timers(c);
+        if ((unsigned int)cv[1] & lgs::kFlagNonFinite) return fail(LGS_ERR_NONFINITE, "%s: a non-finite basis entry or target", fn);
+    } else {
+        for (size_t k = 0; k < (size_t)n_bases * dd; ++k)
+            if (!std::isfinite(bases[k])) return fail(LGS_ERR_NONFINITE, "%s: basis %lld has a non-finite entry", fn, (long long)(k / dd));
+        for (size_t k = 0; k < (size_t)n_bases * td; ++k)
+            if (!std::isfinite(targets[k])) return fail(LGS_ERR_NONFINITE, "%s: a target of basis %lld is not finite", fn, (long long)(k / td));
+    }
+    if (radius2) {
+        const double* r = dev ? rh.data() : radius2;
+        for (size_t k = 0; k < (size_t)n_bases * T; ++k)
+            if (!(r[k] >= 0.0)) return fail(LGS_ERR_INVALID, "radius2[%lld] is NaN or negative", (long long)k);
+    }
+    const lgs_cvp_bases_outputs none{};
+    const lgs_cvp_bases_outputs& o = out ? *out : none;
+    int64_t slice = lgs::kCvpbSlice, slots = lgs::kCvpbSlots;
+    // (hooks build) LGS_TEST_CVPB_SLICE: nodes per problem and launch; LGS_TEST_CVPB_SLOTS: bases of
+    // a chunk -- tests make searches span launches and bases wait for a later chunk
+    if (const char* s = hook("LGS_TEST_CVPB_SLICE")) slice = std::max<int64_t>(1, atoll(s));
+    if (const char* s = hook("LGS_TEST_CVPB_SLOTS")) slots = std::min<int64_t>(lgs::kCvpbSlots, std::max<int64_t>(1, atoll(s)));
+    const int64_t chunk = std::min<int64_t>(n_bases, slots);
+    const int64_t S = chunk * lgs::kCvpLanes;
+    // the workspace: R | CP | c' | state | pstatus | qr_status | z | v | dist2 | nodes | status, and
+    // with host pointers the chunk's bases | targets | radius2
+    size_t top = 0;
+    const auto take = [&](size_t bytes) {
+        const size_t at = top;
+        top += (bytes + 255) / 256 * 256;
+        return at;
+    };
+    const size_t o_R = take((size_t)chunk * dd * 8), o_CP = take((size_t)chunk * d * lgs::kCvpLanes * 8),
+                 o_cp = take((size_t)chunk * td * 8), o_st = take(lgs::cvp_state_bytes((int)d, S)),
+                 o_ps = take((size_t)S * 4), o_qs = take((size_t)chunk * 4), o_z = take((size_t)chunk * td * 8),
+                 o_v = take((size_t)chunk * td * 8), o_d2 = take((size_t)chunk * T * 8),
+                 o_nd = take((size_t)chunk * T * 8), o_su = take((size_t)chunk * T * 4),
+                 o_ib = take(dev ? 0 : (size_t)chunk * dd * 8), o_it = take(dev ? 0 : (size_t)chunk * td * 8),
+                 o_ir = take(dev || !radius2 ? 0 : (size_t)chunk * T * 8);
+    if ((rc = c->CVPB_WS.reserve(top)) || (rc = c->CVPB_LIVE[0].reserve((size_t)chunk * 4)) ||
+        (rc = c->CVPB_LIVE[1].reserve((size_t)chunk * 4)))
+        return rc;
+    char* ws = c->CVPB_WS.as<char>();
+    for (int64_t off = 0; off < n_bases; off += chunk) {
+        const int64_t m = std::min<int64_t>(chunk, n_bases - off);
+        lgs::CvpbArgs a{};
+        a.d = (int)d;
+        a.T = (int)T;
+        a.m = m;
+        a.max_nodes = max_nodes;
+        a.slice = slice;
+        a.R = (double*)(ws + o_R);
+        a.CP = (double*)(ws + o_CP);
+        a.cprime = (double*)(ws + o_cp);
+        a.qr_status = (int32_t*)(ws + o_qs);
+        a.S = S;
+        a.st = lgs::cvp_state_at(ws + o_st, (int)d, S);
+        a.pstatus = (int32_t*)(ws + o_ps);
+        a.ctl = ctl;
+        a.flags = fl;
+        a.z = ws + o_z;
+        a.v = (double*)(ws + o_v);
+        a.dist2 = (double*)(ws + o_d2);
+        a.nodes = (int64_t*)(ws + o_nd);
+        a.status = (int32_t*)(ws + o_su);
+        if (dev) {
+            a.bases = bases + (size_t)off * dd;
+            a.targets = targets + (size_t)off * td;
+            a.radius2 = radius2 ? radius2 + (size_t)off * T : nullptr;
+        } else {
+            a.bases = (const double*)(ws + o_ib);
+            a.targets = (const double*)(ws + o_it);
+            HIP_TRY(hipMemcpyAsync(ws + o_ib, bases + (size_t)off * dd, (size_t)m * dd * 8, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(ws + o_it, targets + (size_t)off * td, (size_t)m * td * 8, hipMemcpyHostToDevice, c->stream));
+            if (radius2) {
+                a.radius2 = (const double*)(ws + o_ir);
+                HIP_TRY(hipMemcpyAsync(ws + o_ir, radius2 + (size_t)off * T, (size_t)m * T * 8, hipMemcpyHostToDevice, c->stream));
+            }
+        }
+        HIP_TRY(hipMemsetAsync(ctl, 0, 16, c->stream));
+        {
+            Scope s(c, 7);
+            HIP_TRY(lgs::launch::cvpb_qr(a, c->stream));
+        }
+        // every launch advances each unfinished problem by `slice` nodes or stops it
+        const double bound = std::ceil((double)max_nodes / (double)slice) + 2.0;
+        int64_t live = m;
+        int cur = 0;
+        for (double launches = 0.0; live > 0; launches += 1.0) {
+            if (launches > bound) return fail(LGS_ERR_HIP, "%s: launch bound exceeded (a library bug)", fn);
+            a.nlive = live;
+            a.live_in = launches == 0.0 ? nullptr : c->CVPB_LIVE[cur ^ 1].as<int32_t>();
+            a.live_out = c->CVPB_LIVE[cur].as<int32_t>();
+            HIP_TRY(hipMemsetAsync(ctl, 0, 8, c->stream));
+            {
+                Scope s(c, 9);
+                HIP_TRY(lgs::launch::cvpb_enum(a, c->stream));
+            }
+            HIP_TRY(hipMemcpyAsync(cv, ctl, 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (cv[0] > (unsigned long long)live) return fail(LGS_ERR_HIP, "%s: live count (a library bug)", fn);
+            live = (int64_t)cv[0];
+            cur ^= 1;
+        }
+        {
+            Scope s(c, 8);
+            HIP_TRY(lgs::launch::cvpb_finish(a, ob, c->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(cv, ctl, 16, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        fold_timers(c);
+        const unsigned int f = (unsigned int)cv[1];
+        if (f & lgs::kFlagNonFinite)
+            return fail(LGS_ERR_NONFINITE, "%s: bases %lld..%lld: a conditional mean is not finite or not below 2^52", fn,
+                        (long long)off, (long long)(off + m - 1));
+        if (f & lgs::kFlagOverflow)
+            return fail(LGS_ERR_OVERFLOW, "%s: coefficient |z| >= 2^31: rerun with LGS_Z64", fn);
+        const auto give = [&](void* user, size_t uoff, const void* src, size_t bytes) {
+            if (!user) return hipSuccess;
+            return hipMemcpyAsync((char*)user + uoff, src, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                                  c->stream);
+        };
+        HIP_TRY(give(z_out, (size_t)off * td * ob, a.z, (size_t)m * td * ob));
+        HIP_TRY(give(v_out, (size_t)off * td * 8, a.v, (size_t)m * td * 8));
+        HIP_TRY(give(o.dist2, (size_t)off * T * 8, a.dist2, (size_t)m * T * 8));
+        HIP_TRY(give(o.nodes, (size_t)off * T * 8, a.nodes, (size_t)m * T * 8));
+        HIP_TRY(give(o.status, (size_t)off * T * 4, a.status, (size_t)m * T * 4));
+        HIP_TRY(give(o.qr_status, (size_t)off * 4, a.qr_status, (size_t)m * 4));
+        HIP_TRY(give(o.R, (size_t)off * dd * 8, a.R, (size_t)m * dd * 8));
+        HIP_TRY(give(o.cprime, (size_t)off * td * 8, a.cprime, (size_t)m * td * 8));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return LGS_OK;
 }
 
 // Exact Gaussian mass: lgs_closest_vector's search with a fixed radius and a weight on every

@@ -16,54 +16,11 @@
 
 #include <cmath>
 
+#include "lgs_cvp_loop.h"
 #include "lgs_kernels.h"
 
 namespace lgs {
 namespace {
-
-// enter(i): the level's conditional centre from the coefficients above it, the nearest
-// integer and the side the zig-zag starts on.  false: the mean is not finite (or beyond
-// 2^52), the search of this target cannot go on.  z / base / sn: the lane's columns of the
-// block's LDS arrays (element i at [i * kCvpLanes]).
-__device__ inline bool cvp_enter(const double* Rs, int d, int i, const double* cpt, int64_t ldc, double* z,
-                                 double* base, double* sn) {
-    const double* Ri = Rs + i * d;
-    double cs = 0.0;
-    int j = i + 1;
-    // (eight LDS reads of each operand in flight per round trip; the sum keeps its order)
-    for (; j + 8 <= d; j += 8) {
-        double rr[8];
-        double zz[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            rr[u] = Ri[j + u];
-            zz[u] = z[(j + u) * kCvpLanes];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) cs = cs + rr[u] * zz[u];
-    }
-    if (j + 4 <= d) {
-        double rr[4];
-        double zz[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            rr[u] = Ri[j + u];
-            zz[u] = z[(j + u) * kCvpLanes];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) cs = cs + rr[u] * zz[u];
-        j += 4;
-    }
-    for (; j < d; ++j) cs = cs + Ri[j] * z[j * kCvpLanes];
-    const double b = cpt[(size_t)i * ldc] - cs;
-    const double m = b / Ri[i];
-    const double zr = rint(m);
-    if (!(fabs(m) < kCvpMaxAbsZ)) return false;
-    base[i * kCvpLanes] = b;
-    z[i * kCvpLanes] = zr;
-    sn[i * kCvpLanes] = m >= zr ? 1.0 : -1.0;
-    return true;
-}
 
 template <typename OT>
 __device__ inline void cvp_finish(const CvpArgs& a, int64_t t, int status, int hb, double A, int64_t nodes,
@@ -146,34 +103,15 @@ __global__ __launch_bounds__(kCvpLanes) void cvp_enum_kernel(const CvpArgs a) {
         }
         ++nodes;
         --budget;
-        const double r = base[i * kCvpLanes] - Rs[i * d + i] * z[i * kCvpLanes];
-        const double Pi = (i == d - 1 ? 0.0 : P[(i + 1) * kCvpLanes]) + r * r;
-        if (Pi < A) {
-            if (i == 0) {  // a closer point; its siblings at level 0 follow
-                A = Pi;
-                hb = 1;
-                for (int k = 0; k < d; ++k) best[(size_t)k * S] = (int64_t)z[k * kCvpLanes];
-            } else {
-                P[i * kCvpLanes] = Pi;
-                --i;
-                if (!cvp_enter(Rs, d, i, a.CP + t, a.ldc, z, base, sn)) {
-                    atomicOr(a.flags, kFlagNonFinite);
-                    cvp_finish<OT>(a, t, 2, 0, A, nodes, best);
-                    t = -1;
-                }
-                continue;
-            }
-        } else {  // every further sibling of this level is farther: back to the parent's next one
-            ++i;
-            if (i == d) {
-                cvp_finish<OT>(a, t, hb ? 0 : 2, hb, A, nodes, best);
-                t = -1;
-                continue;
-            }
+        const CvpStep e = cvp_step(Rs, d, a.CP + t, a.ldc, z, base, P, sn, best, S, i, hb, A);
+        if (e == kCvpBad) {
+            atomicOr(a.flags, kFlagNonFinite);
+            cvp_finish<OT>(a, t, 2, 0, A, nodes, best);
+            t = -1;
+        } else if (e == kCvpDone) {
+            cvp_finish<OT>(a, t, hb ? 0 : 2, hb, A, nodes, best);
+            t = -1;
         }
-        const double w = sn[i * kCvpLanes];  // next sibling: z += stp * (nxt + 1), the side flips
-        z[i * kCvpLanes] += w;
-        sn[i * kCvpLanes] = -(w + (w > 0.0 ? 1.0 : -1.0));
     }
     a.st.tgt[s] = (int32_t)t;
     a.st.lvl[s] = i;

@@ -299,6 +299,48 @@ struct CvpArgs {
     unsigned int* flags;  // the context's flag words (kFlagNonFinite, kFlagOverflow)
 };
 
+// ---- exact closest vector over a batch of bases (lgs_cvpb.hip, lgs_closest_vector_bases;
+// DESIGN.md 6k).  One basis per block of one wave, problem (p, k) -- target k of basis p --
+// on lane k.  Slot q of the chunk's workspace holds basis off + q:
+//   R        m x d x d row-major: the factor (zeros for a refused basis)
+//   CP       m x d x kCvpLanes: c' the way the enumeration reads it, CP[(q d + i) 64 + k]
+//   cprime   m x T x d: the same numbers in the caller's layout
+//   st       a CvpState of S = 64 m slots, problem (q, k) in slot 64 q + k; tgt is the
+//            problem's phase (kCvpbFresh / kCvpbRunning / kCvpbDone)
+//   pstatus  64 m: the status of a done problem (0 / 1 / 2; 3 = its basis was refused)
+constexpr int kCvpbMaxT = 64;             // LGS_CVPB_MAX_T: a wave's lanes
+constexpr int64_t kCvpbSlice = 1 << 16;   // tree nodes a problem advances per launch at most
+constexpr int64_t kCvpbSlots = 1024;      // bases of one chunk (338 MB of workspace at d = T = 64)
+constexpr int kCvpbFresh = 0, kCvpbRunning = 1, kCvpbDone = 2;
+__host__ __device__ inline int cvpb_ld(int d, int T) { return (d + T) | 1; }  // W's row pitch in LDS
+inline size_t cvpb_qr_lds_bytes(int d, int T) { return (size_t)d * cvpb_ld(d, T) * 8; }  // 66 048 B at d = T = 64
+struct CvpbArgs {
+    int d, T;
+    int64_t m;             // bases of the chunk
+    int64_t nlive;         // (cvpb_enum) blocks of this launch
+    int64_t max_nodes, slice;
+    const double* bases;   // m x d x d (the caller's or the staged copy)
+    const double* targets; // m x T x d
+    const double* radius2; // nullable, m x T
+    double* R;
+    double* CP;
+    double* cprime;
+    int32_t* qr_status;    // m
+    int64_t S;             // the state block's slot count (>= 64 m)
+    CvpState st;
+    int32_t* pstatus;
+    const int32_t* live_in;  // (cvpb_enum) nullable: the bases of this launch (none: 0 .. nlive-1)
+    int32_t* live_out;       // the bases with an unfinished problem, ctl[0] of them
+    unsigned long long* ctl;
+    unsigned int* flags;     // one word: kFlagNonFinite, kFlagOverflow
+    // cvpb_finish: the chunk's outputs, in the caller's layout
+    void* z;        // m x T x d, zb-byte elements
+    double* v;      // m x T x d
+    double* dist2;  // m x T
+    int64_t* nodes;
+    int32_t* status;
+};
+
 // ---- LLL basis reduction (lgs_lll.hip, lgs_lll_reduce)
 // One basis per block of one wave.  The block's LDS and the basis's state block in device
 // memory have one layout, in 8-byte words, ld = lll_ld(d) (odd: a column sweep by 32 lanes
@@ -754,6 +796,16 @@ hipError_t cvp_enum(const CvpArgs& a, int zb, hipStream_t st);
 // Slots map[0 .. nlive) of src into slots 0 .. nlive - 1 of dst (blocks of S slots each)
 hipError_t cvp_compact(const CvpState& src, const CvpState& dst, int64_t S, const int32_t* map, int64_t nlive,
                        int d, hipStream_t st);
+// ---- exact closest vector over a batch of bases (lgs_cvpb.hip)
+// cvpb_check: a non-finite value among the n doubles of x sets kFlagNonFinite in *flags.
+// cvpb_qr: QR(p) of the chunk's m bases with their targets into a.R / a.CP / a.cprime /
+// a.qr_status, and every problem's phase (a refused basis: done, status 3).  cvpb_enum: one
+// launch over the a.nlive bases of a.live_in, each problem advanced by at most a.slice nodes.
+// cvpb_finish: z (zb 4 or 8), v, dist2, nodes and status of the chunk's problems.
+hipError_t cvpb_check(const double* x, int64_t n, unsigned int* flags, hipStream_t st);
+hipError_t cvpb_qr(const CvpbArgs& a, hipStream_t st);
+hipError_t cvpb_enum(const CvpbArgs& a, hipStream_t st);
+hipError_t cvpb_finish(const CvpbArgs& a, int zb, hipStream_t st);
 // ---- exact Gaussian mass (lgs_cvp.hip)
 // One launch of the fixed-radius enumeration, as cvp_enum: every slot advances its work item
 // by at most a.slice nodes and takes the next waiting item when it stops.  moments: the

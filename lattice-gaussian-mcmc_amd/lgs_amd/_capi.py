@@ -56,6 +56,7 @@ KERNEL_CPRIME = 7  # lgs_klein_targets: the c' = Q^T t stage (transposes + GEMM)
 KERNEL_DECODE_SELECT = 8  # lgs_klein_decode: the select and gather launches; lgs_imhk_targets: scan and gather
 KERNEL_CVP_ENUM = 9  # lgs_closest_vector: the enumeration launches
 LGS_CVP_MAX_D = 64
+LGS_CVPB_MAX_T = 64          # lgs_closest_vector_bases: targets per basis
 LGS_MASS_MAX_D = 64          # lgs_gaussian_mass
 LGS_MASS_MOMENTS_MAX_D = 40  # ... with sum_z
 LGS_LLL_MAX_D = 64           # lgs_lll_reduce (its launches are timer KERNEL_CVP_ENUM too)
@@ -80,7 +81,7 @@ EXPORTS = ("lgs_version", "lgs_last_error", "lgs_create", "lgs_create_ex", "lgs_
            "lgs_jump_distance", "lgs_marginal_tvd", "lgs_column_range", "lgs_histogram", "lgs_set_decoder", "lgs_nearest_plane",
            "lgs_round_decode", "lgs_counter", "lgs_qskip_elided", "lgs_klein_targets", "lgs_klein_decode",
            "lgs_imhk_targets", "lgs_closest_vector", "lgs_gaussian_mass", "lgs_ball_points", "lgs_exact_table",
-           "lgs_exact_sample", "lgs_lll_reduce", "lgs_bkz_reduce")
+           "lgs_exact_sample", "lgs_lll_reduce", "lgs_bkz_reduce", "lgs_closest_vector_bases")
 
 
 class ImhkOutputs(ctypes.Structure):
@@ -107,6 +108,12 @@ class ImhkTargetsOutputs(ctypes.Structure):
 class CvpOutputs(ctypes.Structure):
     """struct lgs_cvp_outputs (include/lgs.h)."""
     _fields_ = [("dist2", ctypes.c_void_p), ("nodes", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
+class CvpBasesOutputs(ctypes.Structure):
+    """struct lgs_cvp_bases_outputs (include/lgs.h)."""
+    _fields_ = [("dist2", ctypes.c_void_p), ("nodes", ctypes.c_void_p), ("status", ctypes.c_void_p),
+                ("qr_status", ctypes.c_void_p), ("R", ctypes.c_void_p), ("cprime", ctypes.c_void_p)]
 
 
 class MassOutputs(ctypes.Structure):
@@ -247,6 +254,9 @@ def load_library(path: str = LIB_PATH):
     if hasattr(L, "lgs_bkz_reduce"):  # (older A/B baselines lack it)
         L.lgs_bkz_reduce.argtypes = [_vp, _i64, _i64, _vp, _i64, ctypes.c_double, ctypes.c_double, _i64, _i64, _i64,
                                      _vp, _vp, ctypes.POINTER(BkzOutputs), ctypes.c_uint32]
+    if hasattr(L, "lgs_closest_vector_bases"):  # (older A/B baselines lack it)
+        L.lgs_closest_vector_bases.argtypes = [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp,
+                                               ctypes.POINTER(CvpBasesOutputs), ctypes.c_uint32]
     for name in EXPORTS:
         if name not in ("lgs_version", "lgs_last_error") and hasattr(L, name):
             getattr(L, name).restype = ctypes.c_int
@@ -733,6 +743,78 @@ class Context:
             d2, nd, st = np.empty(n), np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int32)
             self.closest_vector(t, max_nodes, r2, z, v, cp, d2, nd, st, f)
             return {"z": _z64(z), "v": v, "cprime": cp, "dist2": d2, "nodes": nd, "status": st}
+        return _host_retry(flags, call)
+
+    # ---------------------------------------------------------------- exact closest vector, a batch of bases
+    @staticmethod
+    def _cvpb_args(bases, targets, max_nodes, flags):
+        """Argument checks of closest_vector_bases / closest_vector_bases_host, before any library
+        call; returns (n, d, T)."""
+        if isinstance(flags, bool) or not isinstance(flags, (int, np.integer)) or flags & ~(LGS_DEVICE_PTRS | LGS_Z64):
+            raise ValueError(f"closest_vector_bases: unsupported flags {flags!r}")
+        shape, tshape = tuple(bases.shape), tuple(targets.shape)
+        if len(shape) != 3 or shape[1] != shape[2]:
+            raise ValueError(f"bases must have shape (n, d, d), got {shape}")
+        n, d = int(shape[0]), int(shape[1])
+        if not 2 <= d <= LGS_CVP_MAX_D:
+            raise ValueError(f"closest_vector_bases supports 2 <= d <= {LGS_CVP_MAX_D}, got d = {d}")
+        if len(tshape) != 3 or tshape[0] != n or tshape[2] != d:
+            raise ValueError(f"targets must have shape ({n}, T, {d}), got {tshape}")
+        T = int(tshape[1])
+        if not 1 <= T <= LGS_CVPB_MAX_T:
+            raise ValueError(f"closest_vector_bases supports 1 <= T <= {LGS_CVPB_MAX_T} targets per basis, got {T}")
+        if isinstance(max_nodes, bool) or not isinstance(max_nodes, (int, np.integer)) or \
+                not 1 <= max_nodes <= 1 << 40:
+            raise ValueError(f"max_nodes must be an integer in 1..2^40, got {max_nodes!r}")
+        return n, d, T
+
+    def closest_vector_bases(self, bases, targets, max_nodes, radius2=None, z_out=None, v_out=None, dist2=None,
+                             nodes=None, status=None, qr_status=None, R=None, cprime=None, flags=0):
+        """Raw lgs_closest_vector_bases on caller buffers (numpy host arrays, or device tensors
+        with LGS_DEVICE_PTRS): bases (n, d, d) float64 whose COLUMNS generate lattice p, targets
+        (n, T, d) float64, problem (p, k) = target k of basis p.  radius2, dist2 (n, T) float64,
+        z_out (n, T, d) int32 (int64 with LGS_Z64), v_out, cprime (n, T, d) float64, nodes (n, T)
+        int64, status (n, T) int32, qr_status (n,) int32, R (n, d, d) float64; all outputs
+        optional.  Needs no loaded basis."""
+        n, d, T = self._cvpb_args(bases, targets, max_nodes, flags)
+        zt = "int64" if flags & LGS_Z64 else "int32"
+        _check_bufs(flags, self.device, ((bases, "float64", "bases"), (targets, "float64", "targets"),
+                                         (radius2, "float64", "radius2"), (z_out, zt, "z_out"),
+                                         (v_out, "float64", "v_out"), (dist2, "float64", "dist2"),
+                                         (nodes, "int64", "nodes"), (status, "int32", "status"),
+                                         (qr_status, "int32", "qr_status"), (R, "float64", "R"),
+                                         (cprime, "float64", "cprime")))
+        self._check_shapes(((radius2, (n, T), "radius2"), (z_out, (n, T, d), "z_out"), (v_out, (n, T, d), "v_out"),
+                            (dist2, (n, T), "dist2"), (nodes, (n, T), "nodes"), (status, (n, T), "status"),
+                            (qr_status, (n,), "qr_status"), (R, (n, d, d), "R"), (cprime, (n, T, d), "cprime")))
+        self._ck(self._L.lgs_closest_vector_bases(
+            self._h, n, d, T, _ptr(bases), _ptr(targets), _ptr(radius2), int(max_nodes), _ptr(z_out), _ptr(v_out),
+            _outputs(CvpBasesOutputs, dist2, nodes, status, qr_status, R, cprime), int(flags)))
+
+    def closest_vector_bases_host(self, bases, targets, max_nodes, radius2=None, *, want_z=True, want_v=True,
+                                  want_R=True, want_cprime=False, flags=0):
+        """Exact closest vectors of host targets (n, T, d) in the lattices of host bases (n, d, d)
+        into fresh host arrays {"z", "v", "dist2", "nodes", "status", "qr_status", "R", "cprime"};
+        int32 coefficients first, int64 on overflow (the same search)."""
+        if isinstance(flags, (int, np.integer)) and not isinstance(flags, bool) and flags & LGS_DEVICE_PTRS:
+            raise ValueError("closest_vector_bases_host takes host arrays")
+        b = np.ascontiguousarray(bases, dtype=np.float64)
+        t = np.ascontiguousarray(targets, dtype=np.float64)
+        n, d, T = self._cvpb_args(b, t, max_nodes, flags)
+        r2 = None
+        if radius2 is not None:
+            r2 = np.ascontiguousarray(radius2, dtype=np.float64)
+            if r2.shape != (n, T) or not np.all(r2 >= 0):
+                raise ValueError(f"radius2 must hold ({n}, {T}) non-negative values")
+
+        def call(f, zdt):
+            z = np.empty((n, T, d), dtype=zdt) if want_z else None
+            v = np.empty((n, T, d)) if want_v else None
+            out = {"dist2": np.empty((n, T)), "nodes": np.empty((n, T), dtype=np.int64),
+                   "status": np.empty((n, T), dtype=np.int32), "qr_status": np.empty(n, dtype=np.int32),
+                   "R": np.empty((n, d, d)) if want_R else None, "cprime": np.empty((n, T, d)) if want_cprime else None}
+            self.closest_vector_bases(b, t, max_nodes, r2, z, v, flags=f, **out)
+            return {"z": _z64(z), "v": v, **out}
         return _host_retry(flags, call)
 
     # ---------------------------------------------------------------- exact Gaussian mass
