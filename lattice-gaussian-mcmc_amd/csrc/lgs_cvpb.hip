@@ -5,6 +5,7 @@
 // cvpb_qr_kernel   one wave per basis: the Householder QR(p) of lgs.h on W = [B_p | targets]
 //                  in LDS, a lane owning a column, so every sum of the definition is a
 //                  lane-private sequential loop and the result is the definition's bit for bit.
+//                  lgs_klein_bases (lgs_kleinb.hip) runs it too, without the search's state.
 // cvpb_enum_kernel one wave per basis, lane k its target k: the search of lgs_cvp.hip (the
 //                  lane state machine of lgs_cvp_loop.h) on the block's own R.  A launch
 //                  advances a problem by at most `slice` nodes, from and to its slot of the
@@ -103,11 +104,12 @@ __global__ __launch_bounds__(kCvpLanes) void cvpb_qr_kernel(const CvpbArgs a) {
     }
     double* Ro = a.R + (size_t)q * d * d;
     for (int e = lane; e < d * d; e += kCvpLanes) Ro[e] = bad ? 0.0 : W[(e / d) * ld + e % d];
-    double* CPo = a.CP + (size_t)q * d * kCvpLanes;
-    for (int i = 0; i < d; ++i) CPo[i * kCvpLanes + lane] = (bad || lane >= T) ? 0.0 : W[i * ld + d + lane];
     double* co = a.cprime + (size_t)q * T * d;
     for (int e = lane; e < T * d; e += kCvpLanes) co[e] = bad ? 0.0 : W[(e % d) * ld + d + e / d];
     if (lane == 0) a.qr_status[q] = bad ? 3 : 0;
+    if (!a.CP) return;  // (cvpb_qr_only: no search follows, no centre store and no state block)
+    double* CPo = a.CP + (size_t)q * d * kCvpLanes;
+    for (int i = 0; i < d; ++i) CPo[i * kCvpLanes + lane] = (bad || lane >= T) ? 0.0 : W[i * ld + d + lane];
     const int64_t s = q * kCvpLanes + lane;
     a.st.tgt[s] = (bad || lane >= T) ? kCvpbDone : kCvpbFresh;
     a.st.lvl[s] = 0;
@@ -269,6 +271,16 @@ hipError_t cvpb_qr(const CvpbArgs& a, hipStream_t st) {
     if (!a.bases || !a.targets || !a.cprime || !a.qr_status) return hipErrorInvalidValue;
     const size_t lds = cvpb_qr_lds_bytes(a.d, a.T);
     if ((e = big_lds((const void*)cvpb_qr_kernel, lds)) != hipSuccess) return e;
+    hipLaunchKernelGGL(cvpb_qr_kernel, dim3((unsigned)a.m), dim3(kCvpLanes), lds, st, a);
+    return hipGetLastError();
+}
+
+hipError_t cvpb_qr_only(const CvpbArgs& a, hipStream_t st) {
+    if (a.d < 2 || a.d > kCvpMaxD || a.T < 1 || a.T > kCvpbMaxT || a.m < 1 || a.CP) return hipErrorInvalidValue;
+    if (!a.bases || !a.targets || !a.R || !a.cprime || !a.qr_status) return hipErrorInvalidValue;
+    const size_t lds = cvpb_qr_lds_bytes(a.d, a.T);
+    const hipError_t e = big_lds((const void*)cvpb_qr_kernel, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(cvpb_qr_kernel, dim3((unsigned)a.m), dim3(kCvpLanes), lds, st, a);
     return hipGetLastError();
 }

@@ -341,6 +341,50 @@ struct CvpbArgs {
     int32_t* status;
 };
 
+// ---- Klein draws over a batch of bases (lgs_kleinb.hip, lgs_klein_bases).
+// The factor and the centres come from cvpb_qr (a CvpbArgs without CP, state block and
+// pstatus).  Lane m of basis q is draw (k, j) = (m / K, m % K) of that basis; a block of
+// kleinb_lanes(d) lanes belongs to one basis.  The chunk's workspace:
+//   ZW   (m T K) x d, zb-byte elements: every draw, in the caller's layout
+//   DW   m T K: the draws' reference-order distances
+constexpr int kKleinbMaxT = 64;               // LGS_KLEINB_MAX_T
+constexpr int64_t kKleinbSlots = 1024;        // bases of one chunk at most
+constexpr int64_t kKleinbMaxDraws = 1 << 22;  // draws of one chunk at most (and T K of a call)
+// Lanes of a block: the z image d x lanes x 8 B beside R has to leave room for a second block
+// at d <= 32 (64 KiB of 160) and to fit at all at d = 64 (64 KiB at 128 lanes).
+__host__ __device__ inline int kleinb_lanes(int d) { return d <= 32 ? 256 : 128; }
+// The targets a block's lanes can touch: L consecutive lanes span at most this many m / K.
+__host__ __device__ inline int kleinb_nt(int T, int64_t K, int L) {
+    const int64_t span = (L + K - 2) / K + 1;
+    return (int)(span < T ? span : T);
+}
+// LDS of a block, in doubles: R (d x d) | R_ii (d) | s_i (d) | c' (d x nt) | z (d x L)
+inline size_t kleinb_lds_bytes(int d, int T, int64_t K) {
+    const int L = kleinb_lanes(d);
+    return ((size_t)d * d + 2 * (size_t)d + (size_t)d * kleinb_nt(T, K, L) + (size_t)d * L) * 8;
+}
+struct KleinbArgs {
+    int d, T, zb, precision;
+    int64_t K;             // draws per target
+    int64_t m;             // bases of the chunk
+    uint64_t seed, base;   // base: the Klein sample index of the chunk's draw (0, 0, 0)
+    const double* bases;   // m x d x d (kleinb_select: v)
+    const double* sigma;   // m
+    const double* R;       // m x d x d
+    const double* cprime;  // m x T x d
+    const int32_t* qr_status;
+    const double* etab;    // SampleZ table (nullptr: the libm path)
+    void* ZW;
+    double* DW;
+    unsigned int* flags;   // one word: kFlagNonFinite, kFlagOverflow
+    // kleinb_select: the chunk's per-problem outputs
+    void* z;               // m x T x d, zb-byte elements
+    double* v;             // m x T x d
+    int64_t* best;         // m x T
+    double* dist2;         // m x T
+    int32_t* status;       // m x T
+};
+
 // ---- LLL basis reduction (lgs_lll.hip, lgs_lll_reduce)
 // One basis per block of one wave.  The block's LDS and the basis's state block in device
 // memory have one layout, in 8-byte words, ld = lll_ld(d) (odd: a column sweep by 32 lanes
@@ -806,6 +850,15 @@ hipError_t cvpb_check(const double* x, int64_t n, unsigned int* flags, hipStream
 hipError_t cvpb_qr(const CvpbArgs& a, hipStream_t st);
 hipError_t cvpb_enum(const CvpbArgs& a, hipStream_t st);
 hipError_t cvpb_finish(const CvpbArgs& a, int zb, hipStream_t st);
+// cvpb_qr for a caller without a search (lgs_klein_bases): the same kernel and arithmetic;
+// a.CP, a.st and a.pstatus may be null and are then not written.
+hipError_t cvpb_qr_only(const CvpbArgs& a, hipStream_t st);
+// ---- Klein draws over a batch of bases (lgs_kleinb.hip)
+// kleinb_draw: every draw of the chunk into a.ZW / a.DW (a refused basis: zero rows, +inf).
+// kleinb_select: per problem the draw with the smallest distance, ties to the smallest index,
+// into a.z / a.v / a.best / a.dist2 / a.status.
+hipError_t kleinb_draw(const KleinbArgs& a, hipStream_t st);
+hipError_t kleinb_select(const KleinbArgs& a, hipStream_t st);
 // ---- exact Gaussian mass (lgs_cvp.hip)
 // One launch of the fixed-radius enumeration, as cvp_enum: every slot advances its work item
 // by at most a.slice nodes and takes the next waiting item when it stops.  moments: the

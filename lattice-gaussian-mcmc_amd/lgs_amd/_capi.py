@@ -57,6 +57,7 @@ KERNEL_DECODE_SELECT = 8  # lgs_klein_decode: the select and gather launches; lg
 KERNEL_CVP_ENUM = 9  # lgs_closest_vector: the enumeration launches
 LGS_CVP_MAX_D = 64
 LGS_CVPB_MAX_T = 64          # lgs_closest_vector_bases: targets per basis
+LGS_KLEINB_MAX_T = 64        # lgs_klein_bases: targets per basis
 LGS_MASS_MAX_D = 64          # lgs_gaussian_mass
 LGS_MASS_MOMENTS_MAX_D = 40  # ... with sum_z
 LGS_LLL_MAX_D = 64           # lgs_lll_reduce (its launches are timer KERNEL_CVP_ENUM too)
@@ -81,7 +82,7 @@ EXPORTS = ("lgs_version", "lgs_last_error", "lgs_create", "lgs_create_ex", "lgs_
            "lgs_jump_distance", "lgs_marginal_tvd", "lgs_column_range", "lgs_histogram", "lgs_set_decoder", "lgs_nearest_plane",
            "lgs_round_decode", "lgs_counter", "lgs_qskip_elided", "lgs_klein_targets", "lgs_klein_decode",
            "lgs_imhk_targets", "lgs_closest_vector", "lgs_gaussian_mass", "lgs_ball_points", "lgs_exact_table",
-           "lgs_exact_sample", "lgs_lll_reduce", "lgs_bkz_reduce", "lgs_closest_vector_bases")
+           "lgs_exact_sample", "lgs_lll_reduce", "lgs_bkz_reduce", "lgs_closest_vector_bases", "lgs_klein_bases")
 
 
 class ImhkOutputs(ctypes.Structure):
@@ -114,6 +115,13 @@ class CvpBasesOutputs(ctypes.Structure):
     """struct lgs_cvp_bases_outputs (include/lgs.h)."""
     _fields_ = [("dist2", ctypes.c_void_p), ("nodes", ctypes.c_void_p), ("status", ctypes.c_void_p),
                 ("qr_status", ctypes.c_void_p), ("R", ctypes.c_void_p), ("cprime", ctypes.c_void_p)]
+
+
+class KleinBasesOutputs(ctypes.Structure):
+    """struct lgs_klein_bases_outputs (include/lgs.h)."""
+    _fields_ = [("best_draw", ctypes.c_void_p), ("dist2", ctypes.c_void_p), ("status", ctypes.c_void_p),
+                ("qr_status", ctypes.c_void_p), ("R", ctypes.c_void_p), ("cprime", ctypes.c_void_p),
+                ("z_draws", ctypes.c_void_p), ("dist2_draws", ctypes.c_void_p)]
 
 
 class MassOutputs(ctypes.Structure):
@@ -257,6 +265,9 @@ def load_library(path: str = LIB_PATH):
     if hasattr(L, "lgs_closest_vector_bases"):  # (older A/B baselines lack it)
         L.lgs_closest_vector_bases.argtypes = [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp,
                                                ctypes.POINTER(CvpBasesOutputs), ctypes.c_uint32]
+    if hasattr(L, "lgs_klein_bases"):  # (older A/B baselines lack it)
+        L.lgs_klein_bases.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
+                                      ctypes.c_int32, _vp, _vp, ctypes.POINTER(KleinBasesOutputs), ctypes.c_uint32]
     for name in EXPORTS:
         if name not in ("lgs_version", "lgs_last_error") and hasattr(L, name):
             getattr(L, name).restype = ctypes.c_int
@@ -814,6 +825,90 @@ class Context:
                    "status": np.empty((n, T), dtype=np.int32), "qr_status": np.empty(n, dtype=np.int32),
                    "R": np.empty((n, d, d)) if want_R else None, "cprime": np.empty((n, T, d)) if want_cprime else None}
             self.closest_vector_bases(b, t, max_nodes, r2, z, v, flags=f, **out)
+            return {"z": _z64(z), "v": v, **out}
+        return _host_retry(flags, call)
+
+    # ---------------------------------------------------------------- Klein draws, a batch of bases
+    @staticmethod
+    def _kleinb_args(bases, targets, sigma, n_draws, precision, flags):
+        """Argument checks of klein_bases / klein_bases_host, before any library call; returns
+        (n, d, T, K)."""
+        if isinstance(flags, bool) or not isinstance(flags, (int, np.integer)) or flags & ~(LGS_DEVICE_PTRS | LGS_Z64):
+            raise ValueError(f"klein_bases: unsupported flags {flags!r}")
+        shape, tshape = tuple(bases.shape), tuple(targets.shape)
+        if len(shape) != 3 or shape[1] != shape[2]:
+            raise ValueError(f"bases must have shape (n, d, d), got {shape}")
+        n, d = int(shape[0]), int(shape[1])
+        if not 2 <= d <= LGS_CVP_MAX_D:
+            raise ValueError(f"klein_bases supports 2 <= d <= {LGS_CVP_MAX_D}, got d = {d}")
+        if len(tshape) != 3 or tshape[0] != n or tshape[2] != d:
+            raise ValueError(f"targets must have shape ({n}, T, {d}), got {tshape}")
+        T = int(tshape[1])
+        if not 1 <= T <= LGS_KLEINB_MAX_T:
+            raise ValueError(f"klein_bases supports 1 <= T <= {LGS_KLEINB_MAX_T} targets per basis, got {T}")
+        if isinstance(n_draws, bool) or not isinstance(n_draws, (int, np.integer)) or n_draws < 1 or \
+                T * int(n_draws) > 1 << 22:
+            raise ValueError(f"n_draws must be a positive integer with T * n_draws <= 2^22, got {n_draws!r}")
+        if isinstance(precision, bool) or not isinstance(precision, (int, np.integer)) or precision < 1:
+            raise ValueError(f"precision must be a positive integer, got {precision!r}")
+        if tuple(sigma.shape) != (n,):
+            raise ValueError(f"sigma must have shape ({n},), got {tuple(sigma.shape)}")
+        return n, d, T, int(n_draws)
+
+    def klein_bases(self, seed, first_sample, bases, targets, sigma, n_draws, precision=10, z_out=None, v_out=None,
+                    best_draw=None, dist2=None, status=None, qr_status=None, R=None, cprime=None, z_draws=None,
+                    dist2_draws=None, flags=0):
+        """Raw lgs_klein_bases on caller buffers (numpy host arrays, or device tensors with
+        LGS_DEVICE_PTRS): bases (n, d, d) float64 whose COLUMNS generate lattice p, targets
+        (n, T, d) float64, sigma (n,) float64; n_draws = K Klein draws around every target.
+        z_out (n, T, d) int32 (int64 with LGS_Z64) and v_out (n, T, d) float64: the closest draw
+        of each target and its lattice point; best_draw (n, T) int64, dist2 (n, T) float64,
+        status (n, T) int32, qr_status (n,) int32, R (n, d, d), cprime (n, T, d), z_draws
+        (n, T, K, d) and dist2_draws (n, T, K); all outputs optional.  Needs no loaded basis."""
+        n, d, T, K = self._kleinb_args(bases, targets, sigma, n_draws, precision, flags)
+        zt = "int64" if flags & LGS_Z64 else "int32"
+        _check_bufs(flags, self.device, ((bases, "float64", "bases"), (targets, "float64", "targets"),
+                                         (sigma, "float64", "sigma"), (z_out, zt, "z_out"),
+                                         (v_out, "float64", "v_out"), (best_draw, "int64", "best_draw"),
+                                         (dist2, "float64", "dist2"), (status, "int32", "status"),
+                                         (qr_status, "int32", "qr_status"), (R, "float64", "R"),
+                                         (cprime, "float64", "cprime"), (z_draws, zt, "z_draws"),
+                                         (dist2_draws, "float64", "dist2_draws")))
+        self._check_shapes(((z_out, (n, T, d), "z_out"), (v_out, (n, T, d), "v_out"), (best_draw, (n, T), "best_draw"),
+                            (dist2, (n, T), "dist2"), (status, (n, T), "status"), (qr_status, (n,), "qr_status"),
+                            (R, (n, d, d), "R"), (cprime, (n, T, d), "cprime"), (z_draws, (n, T, K, d), "z_draws"),
+                            (dist2_draws, (n, T, K), "dist2_draws")))
+        self._ck(self._L.lgs_klein_bases(
+            self._h, int(seed) & (2 ** 64 - 1), int(first_sample) & (2 ** 64 - 1), n, d, T, K, _ptr(bases),
+            _ptr(targets), _ptr(sigma), int(precision), _ptr(z_out), _ptr(v_out),
+            _outputs(KleinBasesOutputs, best_draw, dist2, status, qr_status, R, cprime, z_draws, dist2_draws),
+            int(flags)))
+
+    def klein_bases_host(self, seed, first_sample, bases, targets, sigma, n_draws, precision=10, *, want_z=True,
+                         want_v=True, want_R=True, want_cprime=False, want_draws=False, flags=0):
+        """K Klein draws around each host target (n, T, d) in the lattices of host bases (n, d, d),
+        widths sigma (n,), into fresh host arrays {"z", "v", "best_draw", "dist2", "status",
+        "qr_status", "R", "cprime", "z_draws", "dist2_draws"}; int32 coefficients first, int64 on
+        overflow (the same draws)."""
+        if isinstance(flags, (int, np.integer)) and not isinstance(flags, bool) and flags & LGS_DEVICE_PTRS:
+            raise ValueError("klein_bases_host takes host arrays")
+        b = np.ascontiguousarray(bases, dtype=np.float64)
+        t = np.ascontiguousarray(targets, dtype=np.float64)
+        s = np.ascontiguousarray(sigma, dtype=np.float64)
+        n, d, T, K = self._kleinb_args(b, t, s, n_draws, precision, flags)
+        if not np.all((s > 0) & np.isfinite(s)):
+            raise ValueError("sigma must be positive and finite")
+
+        def call(f, zdt):
+            z = np.empty((n, T, d), dtype=zdt) if want_z else None
+            v = np.empty((n, T, d)) if want_v else None
+            out = {"best_draw": np.empty((n, T), dtype=np.int64), "dist2": np.empty((n, T)),
+                   "status": np.empty((n, T), dtype=np.int32), "qr_status": np.empty(n, dtype=np.int32),
+                   "R": np.empty((n, d, d)) if want_R else None, "cprime": np.empty((n, T, d)) if want_cprime else None,
+                   "z_draws": np.empty((n, T, K, d), dtype=zdt) if want_draws else None,
+                   "dist2_draws": np.empty((n, T, K)) if want_draws else None}
+            self.klein_bases(seed, first_sample, b, t, s, K, precision, z, v, flags=f, **out)
+            out["z_draws"] = _z64(out["z_draws"])
             return {"z": _z64(z), "v": v, **out}
         return _host_retry(flags, call)
 

@@ -2,9 +2,9 @@
 ``src/samplers/__init__.py:3-5``, plus the exact table sampler."""
 from .base import DiscreteGaussianSampler, SamplingStats
 from .klein import RefinedKleinSampler as KleinSampler
-from .klein import RefinedKleinSampler
+from .klein import RefinedKleinSampler, klein_bases
 from .imhk import IMHKSampler
 from .exact import ExactSampler
 
 __all__ = ["DiscreteGaussianSampler", "KleinSampler", "IMHKSampler", "RefinedKleinSampler",
-           "SamplingStats", "ExactSampler"]
+           "SamplingStats", "ExactSampler", "klein_bases"]

@@ -248,3 +248,70 @@ class RefinedKleinSampler(DiscreteGaussianSampler):
 
 
 KleinSampler = RefinedKleinSampler
+
+
+def _bases_inputs(name, bases, targets, sigma, n_draws, rows):
+    """The checks ``klein_bases`` and ``decode.sampling_decode_bases`` share, before any library
+    call: returns (columns (n, d, d), targets (n, T, d) float64, sigma (n,) float64, single)."""
+    b = np.asarray(bases)
+    if b.ndim != 3 or b.shape[1] != b.shape[2]:
+        raise ValueError(f"bases must have shape (n, d, d), got {b.shape}")
+    if b.dtype.kind not in "iuf":
+        raise ValueError(f"bases must be real, got dtype {b.dtype}")
+    n, d = b.shape[0], b.shape[1]
+    if not 2 <= d <= _capi.LGS_CVP_MAX_D:
+        raise ValueError(f"{name} supports 2 <= d <= {_capi.LGS_CVP_MAX_D}, got d = {d}")
+    single = targets is None
+    if targets is None:
+        t3 = np.zeros((n, 1, d))
+    else:
+        t = np.asarray(targets)
+        if t.dtype.kind not in "iuf":
+            raise ValueError(f"targets must be real, got dtype {t.dtype}")
+        t = t.astype(np.float64, copy=False)
+        single = t.ndim == 2
+        t3 = t[:, None, :] if single else t
+        if t3.ndim != 3 or t3.shape[0] != n or t3.shape[2] != d:
+            raise ValueError(f"targets must have shape ({n}, T, {d}) or ({n}, {d}), got {t.shape}")
+    T = t3.shape[1]
+    if not 1 <= T <= _capi.LGS_KLEINB_MAX_T:
+        raise ValueError(f"{name} supports 1 <= T <= {_capi.LGS_KLEINB_MAX_T} targets per basis, got {T}")
+    if isinstance(n_draws, bool) or not isinstance(n_draws, (int, np.integer)) or n_draws < 1 or \
+            T * int(n_draws) > 1 << 22:
+        raise ValueError(f"n_draws must be a positive integer with T * n_draws <= 2^22, got {n_draws!r}")
+    s = np.asarray(sigma)
+    if s.dtype.kind not in "iuf" or s.ndim > 1 or (s.ndim == 1 and s.shape != (n,)):
+        raise ValueError(f"sigma must be a real scalar or an array of shape ({n},), got {sigma!r}")
+    s = np.ascontiguousarray(np.broadcast_to(s.astype(np.float64), (n,)))
+    if not np.all((s > 0) & np.isfinite(s)):
+        raise ValueError("sigma must be positive and finite")
+    cols = np.swapaxes(b, 1, 2) if rows else b
+    return cols, np.ascontiguousarray(t3, dtype=np.float64), s, single
+
+
+def klein_bases(bases, sigma, targets=None, n_draws: int = 1, seed: int = 0, first_sample: int = 0,
+                rows: bool = False, coefficients: bool = False, device: int = 0):
+    """Klein draws in many small lattices at once (``lgs_klein_bases``): ``bases`` (n, d, d),
+    2 <= d <= 64, ``sigma`` a scalar or one width per basis, ``targets`` (n, T, d), T <= 64, and
+    ``n_draws`` = K draws of D_{L_p, sigma_p, t_{p,k}} around each.  The columns of ``bases[p]``
+    generate lattice p; with ``rows=True`` its rows do (``decode.closest_vector_bases``'
+    convention).  The QR factorisation and every draw run on the device; no basis is loaded into
+    a context.  Draw j of target k of basis p is Klein sample ``first_sample + (p T + k) K + j``
+    of ``seed``, whatever the batch.
+
+    Returns the lattice points, shape (n, T, K, d) -- B z of the device's coefficients, formed
+    here -- or ``(points, z)`` with ``coefficients=True`` (int64).  ``targets=None`` means one
+    zero target per basis, and (n, d) targets one target each: the T axis is then dropped.  A
+    basis the QR refuses (a column norm not in (0, inf)) is a ValueError."""
+    from ..decode import _bases_context
+    cols, t3, s, single = _bases_inputs("klein_bases", bases, targets, sigma, n_draws, rows)
+    colsf = np.ascontiguousarray(cols, dtype=np.float64)
+    r = _bases_context(device).klein_bases_host(seed, first_sample, colsf, t3, s, int(n_draws), want_z=False,
+                                                want_v=False, want_R=False, want_draws=True)
+    if r["qr_status"].any():
+        raise ValueError(f"bases {np.flatnonzero(r['qr_status']).tolist()} are singular")
+    z = r["z_draws"]
+    v = np.einsum("nij,ntkj->ntki", colsf, z.astype(np.float64))
+    if single:
+        v, z = v[:, 0], z[:, 0]
+    return (v, z) if coefficients else v
