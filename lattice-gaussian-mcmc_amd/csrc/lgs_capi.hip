@@ -16,6 +16,7 @@
 
 #include "../../include/lgs.h"
 #include "lgs_kernels.h"
+#include "lgs_bz_host.h"
 #include "lgs_mass_host.h"
 #include "lgs_qclean_host.h"
 #include "lgs_szc_host.h"
@@ -186,6 +187,14 @@ struct lgs_ctx {
     DevBuf kchunk, koff;          // per 128-row tile of B: the 64-column chunks with a non-zero digit
     bool bz_mom_ok = false;       // every 64-column chunk has an owner tile (B z can sum the moments)
     DevBuf MP;                    // B z's moment partials per (64-row tile, coordinate)
+    // B z's diagonal-only tiles (bz_lean_kernel; tables of lgs_bz_host.h, one upload):
+    // offd words | B's diagonal | the tiles' owned own chunks
+    DevBuf BZT;
+    size_t bzt_diag = 0, bzt_own = 0;  // byte offsets of the last two
+    bool bz_lean_ok = false;      // some tile of B can be lean: history-sourced launches try it
+    DevBuf BZWL;                  // the worklist of the tiles left to bz_i8_kernel: count, one word per tile
+    DevBuf BZN;                   // device counters: tiles by bz_lean_kernel, by bz_i8_kernel (lgs_bz_tiles)
+    int bz_wl_grid = 0;           // workgroups of the worklist launch: 3 per CU
     DevBuf etab;                  // SampleZ erf/exp table (lgs_device.h erf_gauss)
     DevBuf etab2;                 // its Taylor-coefficient form (lgs_device.h CoefTab)
     DevBuf szc;                   // per-coordinate SampleZ constants (lgs_kernels.h kSzc*)
@@ -404,10 +413,13 @@ struct SetSwap {
 // whose timed Klein launch (every CU, kt0 -> kt1) has finished: the split costs the
 // Klein launches cu_res / split_cus of their time (1/7) and hides the previous block's
 // B z behind them, so it is taken when that block's B z -- its lattice-point stores,
-// 8 d bytes per kept proposal at the ~4.6 TB/s bz_i8_kernel reaches on MI355X -- is the
-// larger.  Measured (bench, same box, profiles/r06bc_bench_cusplit_ab.log): C3 0.26 of
-// the Klein time, split +3.0 %; C4 0.16, +1.6 %; C5 0.13, -3.4 %; C2 0.09, -3.6 %.
-constexpr double kBzStoreBytesPerMs = 4.6e9;
+// 8 d bytes per kept proposal at the ~5.1 TB/s B z reaches on MI355X (bz_lean_kernel: 6.71 ms
+// for the C3 block's 34.4 GB, isolated launches, profiles/r08b_bench_ab.log; 4.6 TB/s
+// before it) -- is the larger.  Measured with bz_i8_kernel alone (bench, same box,
+// profiles/r06bc_bench_cusplit_ab.log): C3 0.26 of the Klein time, split +3.0 %; C4
+// 0.16, +1.6 %; C5 0.13, -3.4 %; C2 0.09, -3.6 %.  With bz_lean_kernel (r08b): C3 split
+// 31.6 ms per step against 34.3 without; C4, C5 and C2 within their noise either way.
+constexpr double kBzStoreBytesPerMs = 5.1e9;
 static int split_decide(lgs_ctx* c) {
     if (c->cu_split != 0 || !c->kt_pending || hipEventQuery(c->kt1) != hipSuccess) return LGS_OK;
     c->kt_pending = false;
@@ -841,13 +853,33 @@ int run_bz(lgs_ctx* c, const void* Z, int zb, int64_t ldz, int64_t n, double* V,
         if (rc) return rc;
         VNP = c->VNP.as<double>();
     }
+    // a launch that reads the last Klein launch's history tries the diagonal-only tiles
+    // first (bz_lean_kernel) when the basis has any; LGS_NO_BZ_LEAN=1: the A/B switch
+    static const bool no_lean = hook_is("LGS_NO_BZ_LEAN", 1);
+    lgs::launch::BzLean lean{};
+    lean.tiles = c->BZN.as<unsigned long long>();
+    if (after_klein && c->hist.Z == Z && Z && c->hist.clive != nullptr && c->bz_lean_ok && c->d % 16 == 0 &&
+        !no_lean) {
+        const int64_t tiles = ((n + 63) / 64) * ((c->d + lgs::kBzBN - 1) / lgs::kBzBN);
+        const int rc = c->BZWL.reserve((size_t)(tiles + 1) * 4);
+        if (rc) return rc;
+        const char* t = c->BZT.as<char>();
+        lean.offd = (const unsigned int*)t;
+        lean.bdiag = (const int*)(t + c->bzt_diag);
+        lean.town = (const unsigned char*)(t + c->bzt_own);
+        lean.wl = c->BZWL.as<unsigned int>();
+        lean.wl_grid = c->bz_wl_grid;
+        // (hooks build: LGS_BZ_LEAN_LDS=bytes, the A/B of the workgroups per CU)
+        static const int pad = hook("LGS_BZ_LEAN_LDS") ? atoi(hook("LGS_BZ_LEAN_LDS")) : lgs::kBzLeanPadLds;
+        lean.pad_lds = pad;
+    }
     HIP_TRY(lgs::launch::bz_i8(Z, zb, ldz, sel, c->kchunk.as<int>(), c->koff.as<int>(), hi, lo,
                                (int)c->bd_cols, (int)c->d, n, V, c->d, b.rb,
                                b.rstride, b.roff, c->flags.as<unsigned int>(),
                                after_klein && c->hist.Z == Z && Z ? c->H16.as<int16_t>() : nullptr, c->hist.lanes,
                                c->hist.cols, c->stream, abort, c->ZNZ.as<uint8_t>(),
                                after_klein && c->hist.Z == Z && Z ? c->hist.clive : nullptr, c->hist.clive_ld,
-                               VNP, vn_n, MP, mp_ld, MPL));
+                               VNP, vn_n, MP, mp_ld, MPL, &lean));
     if (VN) HIP_TRY(lgs::launch::vnorm2_reduce(VNP, (int)c->d, vn_n, b.rb, b.rstride, b.roff, VN, c->stream, abort));
     if (device_replay) {  // the fp64 replay enqueued now, run only if the digit-range flag is set
         c->i8_dev_replay = true;
@@ -2036,6 +2068,27 @@ int lgs_set_basis(lgs_ctx* c, int64_t d, const double* R, const double* cprime, 
             HIP_TRY(hipMemcpy(c->koff.p, ko.data(), ko.size() * 4, hipMemcpyHostToDevice));
             c->bd_rows = rows;
             c->bd_cols = cols;
+            // which blocks of B have nothing off their diagonal, and that diagonal
+            // (bz_lean_kernel)
+            c->bz_lean_ok = false;
+            if (d <= lgs::kOzMaxD) {
+                const lgs::BzTileTables t = lgs::bz_tile_tables(B, d, lgs::kBzOffdWords);
+                c->bzt_diag = t.offd.size() * 4;
+                c->bzt_own = c->bzt_diag + t.bdiag.size() * 4;
+                if ((rc = c->BZT.reserve(c->bzt_own + t.town.size()))) return rc;
+                if (!c->BZN.p) {
+                    if ((rc = c->BZN.reserve(16))) return rc;
+                    HIP_TRY(hipMemset(c->BZN.p, 0, 16));
+                }
+                char* p = c->BZT.as<char>();
+                HIP_TRY(hipMemcpy(p, t.offd.data(), t.offd.size() * 4, hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy(p + c->bzt_diag, t.bdiag.data(), t.bdiag.size() * 4, hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy(p + c->bzt_own, t.town.data(), t.town.size(), hipMemcpyHostToDevice));
+                c->bz_lean_ok = t.any_lean;
+                int ncu = 0;
+                if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) ncu = 0;
+                c->bz_wl_grid = 3 * std::max(ncu, 1);
+            }
         }
     } else {
         c->has_Bi8 = false;
@@ -2835,6 +2888,20 @@ int lgs_qskip_elided(lgs_ctx* c, int reset, uint64_t* value) {
     if (!c) return fail(LGS_ERR_INVALID, "null context");
     if (value) *value = c->n_qskip_elided;
     if (reset) c->n_qskip_elided = 0;
+    return LGS_OK;
+}
+
+int lgs_bz_tiles(lgs_ctx* c, int reset, uint64_t* lean, uint64_t* gemm) {
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    unsigned long long n[2] = {0ull, 0ull};
+    if (c->BZN.p) {  // (device counters: B z runs behind the flag words' copy to the host)
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(n, c->BZN.p, sizeof(n), hipMemcpyDeviceToHost));
+        if (reset) HIP_TRY(hipMemset(c->BZN.p, 0, sizeof(n)));
+    }
+    if (lean) *lean = n[0];
+    if (gemm) *gemm = n[1];
     return LGS_OK;
 }
 

@@ -88,6 +88,16 @@ constexpr int kRecStride = 48;  // 384 bytes, 16-byte multiple
 // B z (bz_i8_kernel): coordinates per workgroup tile (64 was tried: half the
 // accumulators per wave, twice the workgroups)
 constexpr int kBzBN = 128;
+// words per 128-row tile of B in the off-diagonal table (one bit per 64-coordinate chunk,
+// d <= kOzMaxD = 32768)
+constexpr int kBzOffdWords = 32768 / 64 / 32;
+// bz_lean_kernel: unused LDS bytes added to each workgroup's 17 408, so that three fit a
+// 160 KB CU.  The kernel runs beside the next block's Klein launch, on the CUs kept free
+// for it and in whatever a retiring Klein workgroup frees; at the 8 workgroups per CU its
+// 40 VGPRs allow it crowds those slots and delays the Klein launch's own workgroups (C3
+// bench 35.6 ms per step against the parent's 32.9; 5 per CU 34.7, 2 per CU 32.8, 3 per
+// CU 31.5: profiles/r08b_lean_ab.log).
+constexpr int kBzLeanPadLds = 36000;
 static_assert(kRecCbC < kRecStride, "record layout");
 constexpr int kOzCoarse = 4;  // R digits of the far field in coarse panels
 // int8-digit far field layout: per 32-row panel pk >= 1 (K = 32 pk far columns,
@@ -742,6 +752,21 @@ hipError_t transpose_out(const void* Z, int zb, int64_t ldz, int64_t n, int d, v
                          hipStream_t st);
 hipError_t to_coord_major(const void* in, int ib, int64_t n, int d, void* Z, int zb, int64_t ldz,
                           hipStream_t st);
+// B z of a history-sourced launch (clive): bz_lean_kernel for the tiles whose live
+// chunks meet only diagonal blocks of B, bz_i8_kernel from a device worklist for the
+// rest.  offd, bdiag, town: the basis's tables (lgs_bz_host.h); wl: the worklist, one
+// count and one word per tile (null: every tile in bz_i8_kernel's direct grid);
+// wl_grid: workgroups of the worklist launch; tiles (nullable): device counters, [0]
+// tiles bz_lean_kernel computed, [1] tiles bz_i8_kernel did (lgs_bz_tiles).
+struct BzLean {
+    const unsigned int* offd;
+    const int* bdiag;
+    const unsigned char* town;
+    unsigned int* wl;
+    int wl_grid;
+    unsigned long long* tiles;
+    int pad_lds;  // unused LDS bytes added to each bz_lean_kernel workgroup (caps its workgroups per CU)
+};
 // V row of sample s: (s / rb) * rstride + roff + s % rb (rb = n, rstride = roff = 0: row s)
 hipError_t bz(const void* Z, int zb, int64_t ldz, const int64_t* sel, const double* BT, int d,
               int64_t n, double* V, int64_t ldv, int64_t rb, int64_t rstride, int64_t roff,
@@ -753,7 +778,7 @@ hipError_t bz_i8(const void* Z, int zb, int64_t ldz, const int64_t* sel, const i
                  hipStream_t st, const unsigned int* abort = nullptr, const uint8_t* znz = nullptr,
                  const unsigned int* clive = nullptr, int64_t clive_ld = 0, double* VNP = nullptr,
                  int64_t vn_n = 0, unsigned long long* MP = nullptr, int64_t mp_ld = 0,
-                 unsigned int* MPL = nullptr);
+                 unsigned int* MPL = nullptr, const BzLean* lean = nullptr);
 // moments of the kept states from bz_i8's per-(tile, coordinate) partials MP (packed
 // sum over the tile's 64 rows of z^2 * 2^24 + z + 32768; MPL: the tile's live-chunk
 // words, (d + 2047) / 2048 per tile), added to mom (2d); returns at once when *flags has

@@ -80,7 +80,7 @@ EXPORTS = ("lgs_version", "lgs_last_error", "lgs_create", "lgs_create_ex", "lgs_
            "lgs_set_basis", "lgs_klein", "lgs_imhk", "lgs_imhk_trace", "lgs_imhk_ex", "lgs_lattice_points", "lgs_log_density", "lgs_sample_z", "lgs_timing_enable",
            "lgs_timing_get", "lgs_device_info", "lgs_series_stats", "lgs_gram",
            "lgs_jump_distance", "lgs_marginal_tvd", "lgs_column_range", "lgs_histogram", "lgs_set_decoder", "lgs_nearest_plane",
-           "lgs_round_decode", "lgs_counter", "lgs_qskip_elided", "lgs_klein_targets", "lgs_klein_decode",
+           "lgs_round_decode", "lgs_counter", "lgs_qskip_elided", "lgs_bz_tiles", "lgs_klein_targets", "lgs_klein_decode",
            "lgs_imhk_targets", "lgs_closest_vector", "lgs_gaussian_mass", "lgs_ball_points", "lgs_exact_table",
            "lgs_exact_sample", "lgs_lll_reduce", "lgs_bkz_reduce", "lgs_closest_vector_bases", "lgs_klein_bases")
 
@@ -221,6 +221,7 @@ def load_library(path: str = LIB_PATH):
     L.lgs_timing_get.argtypes = [_vp, ctypes.c_int, _dp, _i64p]
     L.lgs_counter.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
     L.lgs_qskip_elided.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
+    L.lgs_bz_tiles.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.lgs_device_info.argtypes = [_vp, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                   _i64p]
     _i64 = ctypes.c_int64
@@ -1377,6 +1378,13 @@ class Context:
         v = ctypes.c_uint64(0)
         self._ck(self._L.lgs_qskip_elided(self._h, 1 if reset else 0, ctypes.byref(v)))
         return v.value
+
+    def bz_tiles(self, reset=False):
+        """lgs_bz_tiles: (lean, gemm) -- the 64 x 128 tiles of the int8-digit lattice points
+        computed without the digit GEMM (diagonal-only blocks of B) and with it."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self._ck(self._L.lgs_bz_tiles(self._h, 1 if reset else 0, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     def device_info(self):
         buf = ctypes.create_string_buffer(256)
