@@ -248,8 +248,8 @@ struct lgs_ctx {
     // lgs_closest_vector_bases: the chunk's workspace (factors, centres, search state, staged
     // inputs and outputs) and the two live lists (its live counter and flag word: CVP_CTL)
     DevBuf CVPB_WS, CVPB_LIVE[2];
-    // lgs_klein_bases: the chunk's workspace (factors, centres, every draw and its distance,
-    // staged inputs and outputs; its flag word: CVP_CTL)
+    // lgs_klein_bases and lgs_imhk_bases: the chunk's workspace (factors, centres, every draw and
+    // its distance or weight, staged inputs and outputs; the flag word: CVP_CTL)
     DevBuf KLB_WS;
     bool has_table = false;
     int64_t tbl_n = 0, tbl_rows = 0;
@@ -3841,6 +3841,43 @@ int lgs_closest_vector_bases(lgs_ctx* c, int64_t n_bases, int64_t d, int64_t T, 
     return LGS_OK;
 }
 
+// The input check lgs_klein_bases and lgs_imhk_bases share, before anything else starts: every
+// basis entry and target finite (device buffers on the device, timer 7), every sigma finite and
+// positive (a device buffer is copied to the host).  Reserves the calls' flag word (CVP_CTL).
+static int kleinb_inputs(lgs_ctx* c, const char* fn, bool dev, int64_t n_bases, int64_t d, int64_t T,
+                         const double* bases, const double* targets, const double* sigma) {
+    const size_t dd = (size_t)d * d, td = (size_t)T * d;
+    int rc;
+    if ((rc = c->CVP_CTL.reserve(16))) return rc;
+    unsigned long long* ctl = c->CVP_CTL.as<unsigned long long>();
+    unsigned int* fl = (unsigned int*)(ctl + 1);
+    unsigned long long cv[2] = {0, 0};
+    std::vector<double> sh;
+    if (dev) {
+        HIP_TRY(hipMemsetAsync(ctl, 0, 16, c->stream));
+        {
+            Scope s(c, 7);
+            HIP_TRY(lgs::launch::cvpb_check(bases, (int64_t)((size_t)n_bases * dd), fl, c->stream));
+            HIP_TRY(lgs::launch::cvpb_check(targets, (int64_t)((size_t)n_bases * td), fl, c->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(cv, ctl, 16, hipMemcpyDeviceToHost, c->stream));
+        sh.resize((size_t)n_bases);
+        HIP_TRY(hipMemcpyAsync(sh.data(), sigma, sh.size() * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        fold_timers(c);
+        if ((unsigned int)cv[1] & lgs::kFlagNonFinite) return fail(LGS_ERR_NONFINITE, "%s: a non-finite basis entry or target", fn);
+    } else {
+        for (size_t k = 0; k < (size_t)n_bases * dd; ++k)
+            if (!std::isfinite(bases[k])) return fail(LGS_ERR_NONFINITE, "%s: basis %lld has a non-finite entry", fn, (long long)(k / dd));
+        for (size_t k = 0; k < (size_t)n_bases * td; ++k)
+            if (!std::isfinite(targets[k])) return fail(LGS_ERR_NONFINITE, "%s: a target of basis %lld is not finite", fn, (long long)(k / td));
+    }
+    const double* s = dev ? sh.data() : sigma;
+    for (int64_t k = 0; k < n_bases; ++k)
+        if (!(s[k] > 0.0) || !std::isfinite(s[k])) return fail(LGS_ERR_INVALID, "sigma[%lld] must be positive and finite", (long long)k);
+    return LGS_OK;
+}
+
 // Klein draws and best-of-K decoding over a batch of bases (lgs_kleinb.hip).  The
 // inputs are checked first, as lgs_closest_vector_bases checks its own; then, per chunk of at
 // most `slots` bases and 2^22 draws: the QR of every basis with its targets (timer 7), every
@@ -3870,35 +3907,10 @@ int lgs_klein_bases(lgs_ctx* c, uint64_t seed, uint64_t first_sample, int64_t n_
     const int ob = (flags & LGS_Z64) ? 8 : 4;
     const int64_t K = n_draws, TK = T * K;
     const size_t dd = (size_t)d * d, td = (size_t)T * d;
-    if ((rc = c->CVP_CTL.reserve(16))) return rc;
+    if ((rc = kleinb_inputs(c, fn, dev, n_bases, d, T, bases, targets, sigma))) return rc;
     unsigned long long* ctl = c->CVP_CTL.as<unsigned long long>();
     unsigned int* fl = (unsigned int*)(ctl + 1);
     unsigned long long cv[2] = {0, 0};
-    std::vector<double> sh;
-    if (dev) {
-        HIP_TRY(hipMemsetAsync(ctl, 0, 16, c->stream));
-        {
-            Scope s(c, 7);
-            HIP_TRY(lgs::launch::cvpb_check(bases, (int64_t)((size_t)n_bases * dd), fl, c->stream));
-            HIP_TRY(lgs::launch::cvpb_check(targets, (int64_t)((size_t)n_bases * td), fl, c->stream));
-        }
-        HIP_TRY(hipMemcpyAsync(cv, ctl, 16, hipMemcpyDeviceToHost, c->stream));
-        sh.resize((size_t)n_bases);
-        HIP_TRY(hipMemcpyAsync(sh.data(), sigma, sh.size() * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        fold_timers(c);
-        if ((unsigned int)cv[1] & lgs::kFlagNonFinite) return fail(LGS_ERR_NONFINITE, "%s: a non-finite basis entry or target", fn);
-    } else {
-        for (size_t k = 0; k < (size_t)n_bases * dd; ++k)
-            if (!std::isfinite(bases[k])) return fail(LGS_ERR_NONFINITE, "%s: basis %lld has a non-finite entry", fn, (long long)(k / dd));
-        for (size_t k = 0; k < (size_t)n_bases * td; ++k)
-            if (!std::isfinite(targets[k])) return fail(LGS_ERR_NONFINITE, "%s: a target of basis %lld is not finite", fn, (long long)(k / td));
-    }
-    {
-        const double* s = dev ? sh.data() : sigma;
-        for (int64_t k = 0; k < n_bases; ++k)
-            if (!(s[k] > 0.0) || !std::isfinite(s[k])) return fail(LGS_ERR_INVALID, "sigma[%lld] must be positive and finite", (long long)k);
-    }
     const lgs_klein_bases_outputs none{};
     const lgs_klein_bases_outputs& o = out ? *out : none;
     int64_t slots = lgs::kKleinbSlots;
@@ -4001,6 +4013,183 @@ int lgs_klein_bases(lgs_ctx* c, uint64_t seed, uint64_t first_sample, int64_t n_
         HIP_TRY(give(o.cprime, (size_t)off * td * 8, a.cprime, (size_t)m * td * 8));
         HIP_TRY(give(o.z_draws, (size_t)off * TK * d * ob, a.ZW, (size_t)m * TK * d * ob));
         HIP_TRY(give(o.dist2_draws, (size_t)off * TK * 8, a.DW, (size_t)m * TK * 8));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return LGS_OK;
+}
+
+// IMHK chains over a batch of bases (lgs_kleinb.hip): lgs_klein_bases' frame --
+// the input check, then per chunk of at most `slots` bases and 2^22 draws the QR (timer 7) and
+// every draw with its Wang-Ling weight (timer 0) -- then every chain's accept scan (timer 2) and
+// the gather of the final and kept states with B z (timer 8).  The chunk's outputs reach the
+// caller only after its flag word came back clean.  No loaded basis is read or touched.
+int lgs_imhk_bases(lgs_ctx* c, uint64_t seed, uint64_t first_chain, int64_t n_bases, int64_t d, int64_t T,
+                   int64_t n_chains, int64_t n_steps, int32_t thin, const double* bases, const double* targets,
+                   const double* sigma, int32_t precision, void* z_out, double* v_out,
+                   const lgs_imhk_bases_outputs* out, uint32_t flags) {
+    const char* const fn = "lgs_imhk_bases";
+    if (!c) return fail(LGS_ERR_INVALID, "null context");
+    if (flags & ~(uint32_t)(LGS_DEVICE_PTRS | LGS_Z64)) return fail(LGS_ERR_INVALID, "%s: unsupported flags 0x%x", fn, flags);
+    if (d < 2 || d > LGS_CVP_MAX_D)
+        return fail(LGS_ERR_INVALID, "%s: d = %lld outside 2..LGS_CVP_MAX_D (%d)", fn, (long long)d, LGS_CVP_MAX_D);
+    if (T < 1 || T > LGS_KLEINB_MAX_T)
+        return fail(LGS_ERR_INVALID, "%s: T = %lld outside 1..LGS_KLEINB_MAX_T (%d)", fn, (long long)T, LGS_KLEINB_MAX_T);
+    if (n_chains < 1 || n_chains > lgs::kKleinbMaxDraws || n_steps < 0 || n_steps >= lgs::kKleinbMaxDraws ||
+        T * n_chains * (n_steps + 1) > lgs::kKleinbMaxDraws)
+        return fail(LGS_ERR_INVALID, "%s: n_chains = %lld, n_steps = %lld: need n_chains >= 1, n_steps >= 0 and "
+                    "T * n_chains * (n_steps + 1) <= 2^22", fn, (long long)n_chains, (long long)n_steps);
+    if (thin < 1) return fail(LGS_ERR_INVALID, "%s: thin must be >= 1", fn);
+    if (precision < 1) return fail(LGS_ERR_INVALID, "precision must be positive");
+    if (n_bases < 0) return fail(LGS_ERR_INVALID, "n_bases < 0");
+    const int64_t C = n_chains, S1 = n_steps + 1, TC = T * C, K = C * S1, TK = T * K, nk = n_steps / thin;
+    // the chain counter has 32 bits
+    if (first_chain > (1ull << 32) || (uint64_t)n_bases > ((1ull << 32) - first_chain) / (uint64_t)TC)
+        return fail(LGS_ERR_INVALID, "%s: first_chain + n_bases * T * n_chains exceeds 2^32", fn);
+    if (n_bases == 0) return LGS_OK;
+    if (!bases || !targets || !sigma) return fail(LGS_ERR_INVALID, "bases, targets and sigma are required");
+    int rc = check_ctx(c, false);
+    if (rc) return rc;
+    const bool dev = (flags & LGS_DEVICE_PTRS) != 0;
+    const int ob = (flags & LGS_Z64) ? 8 : 4;
+    const size_t dd = (size_t)d * d, td = (size_t)T * d;
+    if ((rc = kleinb_inputs(c, fn, dev, n_bases, d, T, bases, targets, sigma))) return rc;
+    unsigned long long* ctl = c->CVP_CTL.as<unsigned long long>();
+    unsigned int* fl = (unsigned int*)(ctl + 1);
+    unsigned long long cv[2] = {0, 0};
+    const lgs_imhk_bases_outputs none{};
+    const lgs_imhk_bases_outputs& o = out ? *out : none;
+    int64_t slots = lgs::kKleinbSlots;
+    // (hooks build) LGS_TEST_KLEINB_SLOTS: bases of a chunk, as in lgs_klein_bases
+    if (const char* s = hook("LGS_TEST_KLEINB_SLOTS")) slots = std::min<int64_t>(lgs::kKleinbSlots, std::max<int64_t>(1, atoll(s)));
+    const int64_t chunk = std::min<int64_t>(n_bases, std::min<int64_t>(slots, std::max<int64_t>(1, lgs::kKleinbMaxDraws / TK)));
+    // the workspace: R | c' | qr_status | every draw | its weight | z | v | logw | accepts |
+    // final_step | status | accepted | the kept states' draws | the kept states, and with host
+    // pointers the chunk's bases | targets | sigma
+    size_t top = 0;
+    const auto take = [&](size_t bytes) {
+        const size_t at = top;
+        top += (bytes + 255) / 256 * 256;
+        return at;
+    };
+    const size_t cc = (size_t)chunk * TC;  // chains of a chunk at most
+    const bool keep = o.z_samples != nullptr;
+    const size_t o_R = take((size_t)chunk * dd * 8), o_cp = take((size_t)chunk * td * 8), o_qs = take((size_t)chunk * 4),
+                 o_zw = take(cc * S1 * d * ob), o_dw = take(cc * S1 * 8), o_z = take(cc * d * ob), o_v = take(cc * d * 8),
+                 o_lw = take(cc * 8), o_ac = take(cc * 8), o_fs = take(cc * 8), o_su = take((size_t)chunk * T * 4),
+                 o_at = take(cc * n_steps), o_sl = take(keep ? cc * nk * 4 : 0), o_zs = take(keep ? cc * nk * d * ob : 0),
+                 o_ib = take(dev ? 0 : (size_t)chunk * dd * 8), o_it = take(dev ? 0 : (size_t)chunk * td * 8),
+                 o_is = take(dev ? 0 : (size_t)chunk * 8);
+    if ((rc = c->KLB_WS.reserve(top + 256))) return rc;
+    char* ws = c->KLB_WS.as<char>();
+    for (int64_t off = 0; off < n_bases; off += chunk) {
+        const int64_t m = std::min<int64_t>(chunk, n_bases - off);
+        const size_t mc = (size_t)m * TC;
+        lgs::CvpbArgs qa{};
+        qa.d = (int)d;
+        qa.T = (int)T;
+        qa.m = m;
+        qa.R = (double*)(ws + o_R);
+        qa.cprime = (double*)(ws + o_cp);
+        qa.qr_status = (int32_t*)(ws + o_qs);
+        lgs::KleinbArgs a{};
+        a.d = (int)d;
+        a.T = (int)T;
+        a.zb = ob;
+        a.precision = precision;
+        a.K = K;
+        a.S1 = S1;
+        a.m = m;
+        a.seed = seed;
+        a.base = first_chain + (uint64_t)off * (uint64_t)TC;
+        a.R = qa.R;
+        a.cprime = qa.cprime;
+        a.qr_status = qa.qr_status;
+        a.etab = c->libm_samplez ? nullptr : c->etab.as<double>();
+        a.ZW = ws + o_zw;
+        a.DW = (double*)(ws + o_dw);
+        a.flags = fl;
+        if (dev) {
+            qa.bases = bases + (size_t)off * dd;
+            qa.targets = targets + (size_t)off * td;
+            a.sigma = sigma + off;
+        } else {
+            qa.bases = (const double*)(ws + o_ib);
+            qa.targets = (const double*)(ws + o_it);
+            a.sigma = (const double*)(ws + o_is);
+            HIP_TRY(hipMemcpyAsync(ws + o_ib, bases + (size_t)off * dd, (size_t)m * dd * 8, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(ws + o_it, targets + (size_t)off * td, (size_t)m * td * 8, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(ws + o_is, sigma + off, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+        }
+        a.bases = qa.bases;
+        lgs::ImhkbArgs s{};
+        s.d = (int)d;
+        s.T = (int)T;
+        s.zb = ob;
+        s.thin = thin;
+        s.C = C;
+        s.S1 = S1;
+        s.m = m;
+        s.n_keep = nk;
+        s.seed = seed;
+        s.base = a.base;
+        s.bases = qa.bases;
+        s.qr_status = qa.qr_status;
+        s.LW = a.DW;
+        s.ZW = a.ZW;
+        s.accepted = (uint8_t*)(ws + o_at);
+        s.accepts = (int64_t*)(ws + o_ac);
+        s.final_step = (int64_t*)(ws + o_fs);
+        s.logw = (double*)(ws + o_lw);
+        s.sel = keep ? (int32_t*)(ws + o_sl) : nullptr;
+        s.z = ws + o_z;
+        s.v = (double*)(ws + o_v);
+        s.status = (int32_t*)(ws + o_su);
+        s.zs = keep ? ws + o_zs : nullptr;
+        HIP_TRY(hipMemsetAsync(ctl, 0, 16, c->stream));
+        {
+            Scope t(c, 7);
+            HIP_TRY(lgs::launch::cvpb_qr_only(qa, c->stream));
+        }
+        {
+            Scope t(c, 0);
+            HIP_TRY(lgs::launch::kleinb_draw_wl(a, c->stream));
+        }
+        {
+            Scope t(c, 2);
+            HIP_TRY(lgs::launch::imhkb_scan(s, c->stream));
+        }
+        {
+            Scope t(c, 8);
+            HIP_TRY(lgs::launch::imhkb_gather(s, c->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(cv, ctl, 16, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        fold_timers(c);
+        const unsigned int f = (unsigned int)cv[1];
+        if (f & lgs::kFlagNonFinite)
+            return fail(LGS_ERR_NONFINITE, "%s: bases %lld..%lld: a conditional mean is not finite or not below 2^52, or a weight "
+                        "is not finite", fn, (long long)off, (long long)(off + m - 1));
+        if (f & lgs::kFlagOverflow)
+            return fail(LGS_ERR_OVERFLOW, "%s: coefficient |z| >= 2^31: rerun with LGS_Z64", fn);
+        const auto give = [&](void* user, size_t uoff, const void* src, size_t bytes) {
+            if (!user || !bytes) return hipSuccess;
+            return hipMemcpyAsync((char*)user + uoff, src, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                                  c->stream);
+        };
+        const size_t c0 = (size_t)off * TC;  // the chunk's first chain
+        HIP_TRY(give(z_out, c0 * d * ob, s.z, mc * d * ob));
+        HIP_TRY(give(v_out, c0 * d * 8, s.v, mc * d * 8));
+        HIP_TRY(give(o.logw, c0 * 8, s.logw, mc * 8));
+        HIP_TRY(give(o.accepts, c0 * 8, s.accepts, mc * 8));
+        HIP_TRY(give(o.final_step, c0 * 8, s.final_step, mc * 8));
+        HIP_TRY(give(o.status, (size_t)off * T * 4, s.status, (size_t)m * T * 4));
+        HIP_TRY(give(o.qr_status, (size_t)off * 4, a.qr_status, (size_t)m * 4));
+        HIP_TRY(give(o.R, (size_t)off * dd * 8, a.R, (size_t)m * dd * 8));
+        HIP_TRY(give(o.cprime, (size_t)off * td * 8, a.cprime, (size_t)m * td * 8));
+        HIP_TRY(give(o.accepted, c0 * n_steps, s.accepted, mc * n_steps));
+        HIP_TRY(give(o.logw_draws, c0 * S1 * 8, a.DW, mc * S1 * 8));
+        HIP_TRY(give(o.z_draws, c0 * S1 * d * ob, a.ZW, mc * S1 * d * ob));
+        HIP_TRY(give(o.z_samples, c0 * nk * d * ob, s.zs, mc * nk * d * ob));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return LGS_OK;

@@ -88,6 +88,13 @@ __device__ __forceinline__ double accept_uniform(uint64_t seed, uint32_t step, u
     return u53(w.x, w.y);
 }
 
+// min(1, exp(lw_y - lw_x)) of that test: 1 from an unweighted state (lw_x = -inf).
+__device__ __forceinline__ double accept_ratio(double lw_y, double lw_x) {
+    if (lw_x == -INFINITY) return 1.0;
+    const double r = exp(lw_y - lw_x);
+    return r < 1.0 ? r : 1.0;  // min(1.0, r); NaN -> 1.0 like Python's min
+}
+
 // Per-lane coordinate uniform stream: slot k = d-1-i, two slots per Philox call.
 template <bool OPAQUE = true>
 struct CoordStreamT {

@@ -393,6 +393,35 @@ struct KleinbArgs {
     int64_t* best;         // m x T
     double* dist2;         // m x T
     int32_t* status;       // m x T
+    // kleinb_draw_wl (lgs_imhk_bases): K = C S1 draws per target, lane m of a basis is draw
+    // t = m % S1 of chain base + q T C + m / S1 (base: the chunk's first chain id), and DW holds
+    // the draws' Wang-Ling log weights (a refused basis: -inf)
+    int64_t S1;            // n_steps + 1
+};
+
+// ---- IMHK chains over a batch of bases (lgs_kleinb.hip, lgs_imhk_bases): the
+// accept scan over the weights kleinb_draw_wl left in LW, and the gather out of its draws ZW.
+// Chain g = (q T + k) C + j of the chunk owns draws g S1 .. g S1 + S1 - 1.
+struct ImhkbArgs {
+    int d, T, zb, thin;
+    int64_t C, S1, m;       // chains per target, n_steps + 1, bases of the chunk
+    int64_t n_keep;         // (S1 - 1) / thin
+    uint64_t seed, base;    // base: the chunk's first chain id
+    const double* bases;    // m x d x d
+    const int32_t* qr_status;
+    const double* LW;       // (m T C) x S1
+    const void* ZW;         // (m T C S1) x d, zb-byte elements
+    // imhkb_scan
+    uint8_t* accepted;      // (m T C) x (S1 - 1)
+    int64_t* accepts;       // m T C
+    int64_t* final_step;    // m T C (-1 for a refused basis)
+    double* logw;           // m T C
+    int32_t* sel;           // (m T C) x n_keep: the state's draw after steps thin, 2 thin, .. (nullable)
+    // imhkb_gather
+    void* z;                // (m T C) x d
+    double* v;              // (m T C) x d
+    int32_t* status;        // m x T
+    void* zs;               // (m T C n_keep) x d (nullable; needs sel)
 };
 
 // ---- LLL basis reduction (lgs_lll.hip, lgs_lll_reduce)
@@ -884,6 +913,13 @@ hipError_t cvpb_qr_only(const CvpbArgs& a, hipStream_t st);
 // into a.z / a.v / a.best / a.dist2 / a.status.
 hipError_t kleinb_draw(const KleinbArgs& a, hipStream_t st);
 hipError_t kleinb_select(const KleinbArgs& a, hipStream_t st);
+// kleinb_draw_wl: kleinb_draw on the counters (chain, step) of lgs_imhk_bases, the Wang-Ling
+// log weight of every draw in a.DW instead of its distance (a refused basis: -inf).
+// imhkb_scan: every chain's Metropolis scan over its S1 weights.  imhkb_gather: the final and the kept states out of
+// the draws, the final states' lattice points and the problems' status.
+hipError_t kleinb_draw_wl(const KleinbArgs& a, hipStream_t st);
+hipError_t imhkb_scan(const ImhkbArgs& a, hipStream_t st);
+hipError_t imhkb_gather(const ImhkbArgs& a, hipStream_t st);
 // ---- exact Gaussian mass (lgs_cvp.hip)
 // One launch of the fixed-radius enumeration, as cvp_enum: every slot advances its work item
 // by at most a.slice nodes and takes the next waiting item when it stops.  moments: the

@@ -2357,11 +2357,6 @@ __device__ double wl_exact_wave(const KleinArgs& a, const double* __restrict__ R
     return lw;
 }
 
-__device__ __forceinline__ double accept_ratio(double lw_y, double lw_x) {
-    if (lw_x == -INFINITY) return 1.0;
-    const double r = exp(lw_y - lw_x);
-    return r < 1.0 ? r : 1.0;  // min(1.0, r); NaN -> 1.0 like Python's min
-}
 // true when u < min(1, exp(lw_y' - lw_x')) is the same for every |lw_x' - lw_x| <= e_x,
 // |lw_y' - lw_y| <= e_y (take: the decision).  The difference of the two computed
 // differences is <= e_x + e_y + 2u(|lw_x| + |lw_y|); exp is monotone to within its

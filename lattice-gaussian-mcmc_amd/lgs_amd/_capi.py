@@ -82,7 +82,8 @@ EXPORTS = ("lgs_version", "lgs_last_error", "lgs_create", "lgs_create_ex", "lgs_
            "lgs_jump_distance", "lgs_marginal_tvd", "lgs_column_range", "lgs_histogram", "lgs_set_decoder", "lgs_nearest_plane",
            "lgs_round_decode", "lgs_counter", "lgs_qskip_elided", "lgs_bz_tiles", "lgs_klein_targets", "lgs_klein_decode",
            "lgs_imhk_targets", "lgs_closest_vector", "lgs_gaussian_mass", "lgs_ball_points", "lgs_exact_table",
-           "lgs_exact_sample", "lgs_lll_reduce", "lgs_bkz_reduce", "lgs_closest_vector_bases", "lgs_klein_bases")
+           "lgs_exact_sample", "lgs_lll_reduce", "lgs_bkz_reduce", "lgs_closest_vector_bases", "lgs_klein_bases",
+           "lgs_imhk_bases")
 
 
 class ImhkOutputs(ctypes.Structure):
@@ -122,6 +123,14 @@ class KleinBasesOutputs(ctypes.Structure):
     _fields_ = [("best_draw", ctypes.c_void_p), ("dist2", ctypes.c_void_p), ("status", ctypes.c_void_p),
                 ("qr_status", ctypes.c_void_p), ("R", ctypes.c_void_p), ("cprime", ctypes.c_void_p),
                 ("z_draws", ctypes.c_void_p), ("dist2_draws", ctypes.c_void_p)]
+
+
+class ImhkBasesOutputs(ctypes.Structure):
+    """struct lgs_imhk_bases_outputs (include/lgs.h)."""
+    _fields_ = [("logw", ctypes.c_void_p), ("accepts", ctypes.c_void_p), ("final_step", ctypes.c_void_p),
+                ("status", ctypes.c_void_p), ("qr_status", ctypes.c_void_p), ("R", ctypes.c_void_p),
+                ("cprime", ctypes.c_void_p), ("accepted", ctypes.c_void_p), ("logw_draws", ctypes.c_void_p),
+                ("z_draws", ctypes.c_void_p), ("z_samples", ctypes.c_void_p)]
 
 
 class MassOutputs(ctypes.Structure):
@@ -269,6 +278,10 @@ def load_library(path: str = LIB_PATH):
     if hasattr(L, "lgs_klein_bases"):  # (older A/B baselines lack it)
         L.lgs_klein_bases.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
                                       ctypes.c_int32, _vp, _vp, ctypes.POINTER(KleinBasesOutputs), ctypes.c_uint32]
+    if hasattr(L, "lgs_imhk_bases"):  # (older A/B baselines lack it)
+        L.lgs_imhk_bases.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, _i64, _i64, _i64, _i64, _i64, ctypes.c_int32,
+                                     _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, ctypes.POINTER(ImhkBasesOutputs),
+                                     ctypes.c_uint32]
     for name in EXPORTS:
         if name not in ("lgs_version", "lgs_last_error") and hasattr(L, name):
             getattr(L, name).restype = ctypes.c_int
@@ -910,6 +923,116 @@ class Context:
                    "dist2_draws": np.empty((n, T, K)) if want_draws else None}
             self.klein_bases(seed, first_sample, b, t, s, K, precision, z, v, flags=f, **out)
             out["z_draws"] = _z64(out["z_draws"])
+            return {"z": _z64(z), "v": v, **out}
+        return _host_retry(flags, call)
+
+    # ---------------------------------------------------------------- IMHK chains, a batch of bases
+    @staticmethod
+    def _imhkb_args(bases, targets, sigma, n_chains, n_steps, thin, precision, flags):
+        """Argument checks of imhk_bases / imhk_bases_host, before any library call; returns
+        (n, d, T, C, S, n_keep)."""
+        if isinstance(flags, bool) or not isinstance(flags, (int, np.integer)) or flags & ~(LGS_DEVICE_PTRS | LGS_Z64):
+            raise ValueError(f"imhk_bases: unsupported flags {flags!r}")
+        shape, tshape = tuple(bases.shape), tuple(targets.shape)
+        if len(shape) != 3 or shape[1] != shape[2]:
+            raise ValueError(f"bases must have shape (n, d, d), got {shape}")
+        n, d = int(shape[0]), int(shape[1])
+        if not 2 <= d <= LGS_CVP_MAX_D:
+            raise ValueError(f"imhk_bases supports 2 <= d <= {LGS_CVP_MAX_D}, got d = {d}")
+        if len(tshape) != 3 or tshape[0] != n or tshape[2] != d:
+            raise ValueError(f"targets must have shape ({n}, T, {d}), got {tshape}")
+        T = int(tshape[1])
+        if not 1 <= T <= LGS_KLEINB_MAX_T:
+            raise ValueError(f"imhk_bases supports 1 <= T <= {LGS_KLEINB_MAX_T} targets per basis, got {T}")
+        if isinstance(n_chains, bool) or not isinstance(n_chains, (int, np.integer)) or n_chains < 1:
+            raise ValueError(f"n_chains must be a positive integer, got {n_chains!r}")
+        if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or n_steps < 0:
+            raise ValueError(f"n_steps must be a non-negative integer, got {n_steps!r}")
+        C, S = int(n_chains), int(n_steps)
+        if T * C * (S + 1) > 1 << 22:
+            raise ValueError(f"imhk_bases needs T * n_chains * (n_steps + 1) <= 2^22, got {T} * {C} * {S + 1}")
+        if isinstance(thin, bool) or not isinstance(thin, (int, np.integer)) or not 1 <= thin < 1 << 31:
+            raise ValueError(f"thin must be a positive integer, got {thin!r}")
+        if isinstance(precision, bool) or not isinstance(precision, (int, np.integer)) or precision < 1:
+            raise ValueError(f"precision must be a positive integer, got {precision!r}")
+        if tuple(sigma.shape) != (n,):
+            raise ValueError(f"sigma must have shape ({n},), got {tuple(sigma.shape)}")
+        return n, d, T, C, S, S // int(thin)
+
+    @staticmethod
+    def _imhkb_chains(first_chain, n, T, C):
+        if isinstance(first_chain, bool) or not isinstance(first_chain, (int, np.integer)) or first_chain < 0 or \
+                int(first_chain) + n * T * C > 1 << 32:
+            raise ValueError(f"first_chain must be a non-negative integer with first_chain + n * T * n_chains <= 2^32, "
+                             f"got {first_chain!r}")
+
+    def imhk_bases(self, seed, first_chain, bases, targets, sigma, n_chains, n_steps, thin=1, precision=10, z_out=None,
+                   v_out=None, logw=None, accepts=None, final_step=None, status=None, qr_status=None, R=None,
+                   cprime=None, accepted=None, logw_draws=None, z_draws=None, z_samples=None, flags=0):
+        """Raw lgs_imhk_bases on caller buffers (numpy host arrays, or device tensors with
+        LGS_DEVICE_PTRS): bases (n, d, d) float64 whose COLUMNS generate lattice p, targets
+        (n, T, d) float64, sigma (n,) float64; C = n_chains IMHK chains of S = n_steps steps with
+        Wang-Ling weights around every target, chain j of target k of basis p being chain
+        first_chain + (p T + k) C + j.  z_out (n, T, C, d) int32 (int64 with LGS_Z64) and v_out
+        (n, T, C, d) float64: the final states and their lattice points; logw (n, T, C) float64,
+        accepts / final_step (n, T, C) int64, status (n, T) int32, qr_status (n,) int32, R
+        (n, d, d), cprime (n, T, d), accepted (n, T, C, S) uint8, logw_draws (n, T, C, S + 1),
+        z_draws (n, T, C, S + 1, d) and z_samples (n, T, C, S // thin, d): the state after steps
+        thin, 2 thin, ..; all outputs optional.  Needs no loaded basis."""
+        n, d, T, C, S, nk = self._imhkb_args(bases, targets, sigma, n_chains, n_steps, thin, precision, flags)
+        self._imhkb_chains(first_chain, n, T, C)
+        zt = "int64" if flags & LGS_Z64 else "int32"
+        _check_bufs(flags, self.device, ((bases, "float64", "bases"), (targets, "float64", "targets"),
+                                         (sigma, "float64", "sigma"), (z_out, zt, "z_out"),
+                                         (v_out, "float64", "v_out"), (logw, "float64", "logw"),
+                                         (accepts, "int64", "accepts"), (final_step, "int64", "final_step"),
+                                         (status, "int32", "status"), (qr_status, "int32", "qr_status"),
+                                         (R, "float64", "R"), (cprime, "float64", "cprime"),
+                                         (accepted, "uint8", "accepted"), (logw_draws, "float64", "logw_draws"),
+                                         (z_draws, zt, "z_draws"), (z_samples, zt, "z_samples")))
+        self._check_shapes(((z_out, (n, T, C, d), "z_out"), (v_out, (n, T, C, d), "v_out"), (logw, (n, T, C), "logw"),
+                            (accepts, (n, T, C), "accepts"), (final_step, (n, T, C), "final_step"),
+                            (status, (n, T), "status"), (qr_status, (n,), "qr_status"), (R, (n, d, d), "R"),
+                            (cprime, (n, T, d), "cprime"), (accepted, (n, T, C, S), "accepted"),
+                            (logw_draws, (n, T, C, S + 1), "logw_draws"), (z_draws, (n, T, C, S + 1, d), "z_draws"),
+                            (z_samples, (n, T, C, nk, d), "z_samples")))
+        self._ck(self._L.lgs_imhk_bases(
+            self._h, int(seed) & (2 ** 64 - 1), int(first_chain), n, d, T, C, S, int(thin), _ptr(bases), _ptr(targets),
+            _ptr(sigma), int(precision), _ptr(z_out), _ptr(v_out),
+            _outputs(ImhkBasesOutputs, logw, accepts, final_step, status, qr_status, R, cprime, accepted, logw_draws,
+                     z_draws, z_samples), int(flags)))
+
+    def imhk_bases_host(self, seed, first_chain, bases, targets, sigma, n_chains, n_steps, thin=1, precision=10, *,
+                        want_z=True, want_v=True, want_R=True, want_cprime=False, want_trace=False,
+                        want_samples=False, flags=0):
+        """C IMHK chains of S steps around each host target (n, T, d) in the lattices of host bases
+        (n, d, d), widths sigma (n,), into fresh host arrays {"z", "v", "logw", "accepts",
+        "final_step", "status", "qr_status", "R", "cprime"}, with want_trace also "accepted",
+        "logw_draws" and "z_draws", with want_samples "z_samples"; int32 coefficients first,
+        int64 on overflow (the same chains)."""
+        if isinstance(flags, (int, np.integer)) and not isinstance(flags, bool) and flags & LGS_DEVICE_PTRS:
+            raise ValueError("imhk_bases_host takes host arrays")
+        b = np.ascontiguousarray(bases, dtype=np.float64)
+        t = np.ascontiguousarray(targets, dtype=np.float64)
+        s = np.ascontiguousarray(sigma, dtype=np.float64)
+        n, d, T, C, S, nk = self._imhkb_args(b, t, s, n_chains, n_steps, thin, precision, flags)
+        self._imhkb_chains(first_chain, n, T, C)
+        if not np.all((s > 0) & np.isfinite(s)):
+            raise ValueError("sigma must be positive and finite")
+
+        def call(f, zdt):
+            z = np.empty((n, T, C, d), dtype=zdt) if want_z else None
+            v = np.empty((n, T, C, d)) if want_v else None
+            out = {"logw": np.empty((n, T, C)), "accepts": np.empty((n, T, C), dtype=np.int64),
+                   "final_step": np.empty((n, T, C), dtype=np.int64), "status": np.empty((n, T), dtype=np.int32),
+                   "qr_status": np.empty(n, dtype=np.int32), "R": np.empty((n, d, d)) if want_R else None,
+                   "cprime": np.empty((n, T, d)) if want_cprime else None,
+                   "accepted": np.empty((n, T, C, S), dtype=np.uint8) if want_trace else None,
+                   "logw_draws": np.empty((n, T, C, S + 1)) if want_trace else None,
+                   "z_draws": np.empty((n, T, C, S + 1, d), dtype=zdt) if want_trace else None,
+                   "z_samples": np.empty((n, T, C, nk, d), dtype=zdt) if want_samples else None}
+            self.imhk_bases(seed, first_chain, b, t, s, C, S, int(thin), precision, z, v, flags=f, **out)
+            out["z_draws"], out["z_samples"] = _z64(out["z_draws"]), _z64(out["z_samples"])
             return {"z": _z64(z), "v": v, **out}
         return _host_retry(flags, call)
 

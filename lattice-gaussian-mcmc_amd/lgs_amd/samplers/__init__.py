@@ -3,8 +3,8 @@
 from .base import DiscreteGaussianSampler, SamplingStats
 from .klein import RefinedKleinSampler as KleinSampler
 from .klein import RefinedKleinSampler, klein_bases
-from .imhk import IMHKSampler
+from .imhk import IMHKSampler, imhk_bases
 from .exact import ExactSampler
 
 __all__ = ["DiscreteGaussianSampler", "KleinSampler", "IMHKSampler", "RefinedKleinSampler",
-           "SamplingStats", "ExactSampler", "klein_bases"]
+           "SamplingStats", "ExactSampler", "klein_bases", "imhk_bases"]

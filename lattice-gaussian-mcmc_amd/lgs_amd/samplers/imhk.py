@@ -364,3 +364,72 @@ class IMHKSampler(DiscreteGaussianSampler):
         rate = self.stats.acceptance_rate or 0.0
         name = getattr(self.lattice, "name", type(self.lattice).__name__)
         return f"IMHKSampler(lattice={name}, σ={self.sigma:.4f}, burn_in={self.burn_in}, acceptance_rate={rate:.2%})"
+
+
+def imhk_bases(bases, sigma, targets=None, n_chains: int = 1, n_steps: int = 32, thin=None, seed: int = 0,
+               first_chain: int = 0, rows: bool = False, reduce: bool = False, coefficients: bool = False,
+               device: int = 0, context=None):
+    """IMHK chains in many small lattices at once (``lgs_imhk_bases``): ``bases`` (n, d, d),
+    2 <= d <= 64, ``sigma`` a scalar or one width per basis, ``targets`` (n, T, d), T <= 64, and
+    ``n_chains`` = C independent Metropolis-Hastings-Klein chains of ``n_steps`` steps with exact
+    Wang-Ling weights around each target -- samples of D_{L_p, sigma_p, t_{p,k}} at widths where
+    ``klein_bases``' draws are biased.  ``rows`` as in ``klein_bases``.  The QR factorisation, the
+    draws, the accept scan and B z run on the device; no basis is loaded into a context.  Chain j
+    of target k of basis p is chain ``first_chain + (p T + k) C + j`` of ``seed``, whatever the
+    batch.
+
+    Returns the chains' final states as lattice points, shape (n, T, C, d), or with ``thin`` the
+    states after steps thin, 2 thin, .., shape (n, T, C, n_steps // thin, d); ``(points, z)`` with
+    ``coefficients=True`` (int64, in the caller's basis).  ``targets=None`` means one zero target
+    per basis, and (n, d) targets one target each: the T axis is then dropped.  A basis the QR
+    refuses is a ValueError.
+
+    ``reduce=True`` (integral bases): the batched ``lll_reduce`` runs first and the chains run on
+    the reduced bases, where they mix faster; a basis whose LLL status is not 0 is used unreduced.
+    The law over lattice points is unchanged; coefficients are mapped back with the integer U
+    (``decode.map_coefficients``) and the points are formed from the caller's basis."""
+    from ..decode import _bases_context, _points, map_coefficients
+    from .klein import _bases_inputs
+    for name, val, low in (("n_chains", n_chains, 1), ("n_steps", n_steps, 0)):
+        if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or val < low:
+            raise ValueError(f"{name} must be an integer >= {low}, got {val!r}")
+    if thin is not None and (isinstance(thin, bool) or not isinstance(thin, (int, np.integer)) or thin < 1):
+        raise ValueError(f"thin must be None or a positive integer, got {thin!r}")
+    cols, t3, s, single = _bases_inputs("imhk_bases", bases, targets, sigma, 1, rows)
+    n, d, T = cols.shape[0], cols.shape[1], t3.shape[1]
+    C, S = int(n_chains), int(n_steps)
+    if T * C * (S + 1) > 1 << 22:
+        raise ValueError(f"imhk_bases needs T * n_chains * (n_steps + 1) <= 2^22, got {T} * {C} * {S + 1}")
+    if isinstance(first_chain, bool) or not isinstance(first_chain, (int, np.integer)) or first_chain < 0 or \
+            int(first_chain) + n * T * C > 1 << 32:
+        raise ValueError(f"first_chain must be a non-negative integer with first_chain + n * T * n_chains <= 2^32, "
+                         f"got {first_chain!r}")
+    U = None
+    if reduce:
+        from ..reduction import _integral
+        ib = np.ascontiguousarray(_integral(cols))
+    ctx = context if context is not None else _bases_context(device)
+    work = cols
+    if reduce:
+        lr = ctx.lll_reduce_host(ib)
+        ok = lr["status"] == 0
+        U = np.where(ok[:, None, None], lr["U"], np.eye(d, dtype=np.int64)[None])
+        work = np.where(ok[:, None, None], lr["basis"], ib)
+    r = ctx.imhk_bases_host(seed, first_chain, np.ascontiguousarray(work, dtype=np.float64), t3, s, C, S,
+                            1 if thin is None else int(thin), want_z=thin is None, want_v=thin is None and not reduce,
+                            want_R=False, want_samples=thin is not None)
+    if r["qr_status"].any():
+        raise ValueError(f"bases {np.flatnonzero(r['qr_status']).tolist()} are singular")
+    z = r["z"] if thin is None else r["z_samples"]
+    tail = z.shape[1:]
+    if U is not None:
+        z = map_coefficients(U, z.reshape(n, -1, d)).reshape((n,) + tail)
+    if thin is None and not reduce:
+        v = r["v"]
+    else:  # the sequential sum of lgs_closest_vector_bases, in the caller's basis
+        colsf = np.asarray(cols, dtype=np.float64)
+        v = (np.stack([_points(colsf[p], z[p].reshape(-1, d)) for p in range(n)]) if n else np.zeros(z.shape))
+        v = v.reshape((n,) + tail)
+    if single:
+        v, z = v[:, 0], z[:, 0]
+    return (v, z) if coefficients else v
