@@ -50,6 +50,7 @@ class _State:
         self.tours = self.blocks = self.insertions = self.nodes = self.truncated = 0
         self.steps = 0  # Euclid steps of INSERT applied
         self.log = []  # per block: (kb, e, nodes_b, trunc, best or None)
+        self.trace = []  # in order: ("lll", main-loop iterations of one run) and ("enum", nodes of one block)
 
     def chol(self, k):
         mu, r = self.mu, self.r
@@ -64,6 +65,13 @@ class _State:
 
     def lll(self, k):
         """The main loop of lgs_lll_reduce entered at k; returns when k reaches d."""
+        start = self.iters
+        try:
+            self._lll(k)
+        finally:
+            self.trace.append(("lll", self.iters - start))
+
+    def _lll(self, k):
         d, b, U, G, mu, r, eta = self.d, self.b, self.U, self.G, self.mu, self.r, self.eta
         while k < d:
             if self.iters == self.max_iters:
@@ -202,7 +210,11 @@ class _State:
         ins = 0
         for kb in range(d - 1):
             e = min(kb + block_size, d) - 1
-            best, trunc, nodes_b = self.enum(kb, e, enum_nodes, plain)
+            before = self.nodes
+            try:
+                best, trunc, nodes_b = self.enum(kb, e, enum_nodes, plain)
+            finally:
+                self.trace.append(("enum", self.nodes - before))
             self.blocks += 1
             self.truncated += trunc
             self.log.append((kb, e, nodes_b, trunc, best))
@@ -225,14 +237,15 @@ class _State:
                 "swaps": self.swaps, "iters": self.iters, "passes": self.passes, "tours": self.tours,
                 "blocks": self.blocks, "insertions": self.insertions, "nodes": self.nodes,
                 "truncated": self.truncated, "status": status, "gs_norm2": [self.r[i][i] for i in range(d)],
-                "log": self.log}
+                "log": self.log, "trace": self.trace}
 
 
 def bkz(basis, block_size, delta=0.99, eta=0.51, max_tours=1 << 40, max_iters=1 << 40, enum_nodes=1 << 40,
         plain=False):
     """lgs_bkz_reduce of one basis.  Returns a dict with the fields of FIELDS and ``log``, the
     list of (kb, e, nodes_b, trunc, best) per block enumeration, ``where`` (the part of the definition
-    that stopped the call: "lll", "enum", "insert" or "tour") and ``steps`` (Euclid steps applied)."""
+    that stopped the call: "lll", "enum", "insert" or "tour"), ``steps`` (Euclid steps applied) and
+    ``trace``, the LLL runs and block enumerations in order with what each spent (for schedule())."""
     s = _State(basis, delta, eta, max_iters)
     try:
         s.chol(0)
@@ -279,6 +292,71 @@ def reduced(name, block_size, delta=0.99, **kw):
     if key not in _cache:
         _cache[key] = bkz(basis(name).tolist(), block_size, delta, 0.51, **kw)
     return _cache[key]
+
+
+# (name, block_size, max_tours), all at (0.99, 0.51): the dense signed bases of lll_oracle at the
+# d where the ownership of lanes changes, and the two rounding ties that half-even and half-away
+# resolve differently (lll_loop is shared).  dense63 runs one tour: the oracle needs 0.8 s for it.
+DENSE_CASES = (("dense7", 4, 1 << 40), ("dense17", 6, 1 << 40), ("dense33", 10, 1 << 40), ("dense63", 8, 1),
+               ("tie2.5", 2, 1 << 40), ("tie-2.5", 2, 1 << 40))
+
+
+def schedule(o, lll_slice=LLL_SLICE, node_slice=BKZ_SLICE):
+    """What the kernel's state machine makes of one oracle result under forced slices: (reduction
+    launches, suspensions inside an LLL run, suspensions inside an enumeration).  A launch has
+    lll_slice main-loop iterations and node_slice nodes to spend on whatever comes, in the order of
+    o["trace"]; it suspends the basis when a run or a block needs one more than is left (both
+    loops test their own end -- k = d, max_iters, enum_nodes, the block exhausted -- before the
+    budget, so spending the last of a budget on the last step suspends nothing)."""
+    launches, in_lll, in_enum = 1, 0, 0
+    left = {"lll": lll_slice, "enum": node_slice}
+    for kind, n in o["trace"]:
+        while n > left[kind]:
+            n -= left[kind]
+            launches += 1
+            in_lll += kind == "lll"
+            in_enum += kind == "enum"
+            left = {"lll": lll_slice, "enum": node_slice}
+        left[kind] -= n
+    return launches, in_lll, in_enum
+
+
+MIXED_D, MIXED_BETA = 17, 6
+MIXED_DENSE = ((500, 3), (500, 1000), (501, 1000), (502, 3), (503, 30), (504, 1000))  # (seed, amp)
+_mixed = {}
+
+
+def mixed_batch():
+    """The d = 17 batch of the scheduling test, (n, 17, 17) int64: six dense bases, and among them
+    the entries that leave the live list early -- the identity, a BKZ-reduced basis (the oracle's
+    output for the first entry), a singular matrix -- and a repeat.  Not to be modified."""
+    if "bases" not in _mixed:
+        d = MIXED_D
+        ds = [lll_oracle.dense(d, s, amp) for s, amp in MIXED_DENSE]
+        red = np.array(bkz(ds[0].tolist(), MIXED_BETA)["basis_out"], dtype=np.int64)
+        sing = lll_oracle.dense(d, 7002, 30).copy()
+        sing[:, 9] = sing[:, 3] + sing[:, 6]
+        _mixed["bases"] = np.ascontiguousarray(
+            np.stack([ds[0], np.eye(d, dtype=np.int64), ds[1], ds[2], sing, ds[3], red, ds[4], ds[1], ds[5]]))
+    return _mixed["bases"]
+
+
+MIXED_MAX_TOURS = 2  # the budget of the run in which status 4 and status 0 meet
+
+
+def mixed_reduced(max_tours=1 << 40):
+    """bkz() of every entry of mixed_batch() at beta = MIXED_BETA, (0.99, 0.51), once per process."""
+    if max_tours not in _mixed:
+        _mixed[max_tours] = [bkz(x.tolist(), MIXED_BETA, max_tours=max_tours) for x in mixed_batch()]
+    return _mixed[max_tours]
+
+
+def chunk_reduced():
+    """index of lll_oracle.chunk_batch() -> bkz() at beta = 2, (0.99, 0.51), once per process."""
+    if "chunk" not in _mixed:
+        B, idx = lll_oracle.chunk_batch()
+        _mixed["chunk"] = {v: bkz(B[idx.index(v)].tolist(), 2) for v in sorted(set(idx))}
+    return _mixed["chunk"]
 
 
 GUARD_SCALE = 25600000

@@ -302,3 +302,93 @@ def test_oracle_stops_and_guards():
     assert (r["status"], r["where"], r["steps"], r["insertions"], r["blocks"]) == (2, "insert", 1, 0, 1)
     assert r["basis_out"] != G and lll_oracle.matmul(G, r["U_out"]) == r["basis_out"]
     assert abs(lll_oracle.det_bareiss(r["U_out"])) == 1
+
+
+# ---------------------------------------------------------------- premises of the dense and the scheduling cases
+@pytest.mark.parametrize("name,beta,max_tours", bkz_oracle.DENSE_CASES)
+def test_dense_cases_return_a_unimodular_transform(name, beta, max_tours):
+    B = bkz_oracle.basis(name).tolist()
+    r = bkz_oracle.reduced(name, beta, max_tours=max_tours)
+    print(f"  {name} beta {beta}: status {r['status']}, tours {r['tours']}, blocks {r['blocks']}, insertions "
+          f"{r['insertions']}, nodes {r['nodes']}, iters {r['iters']}")
+    assert r["status"] == (4 if name == "dense63" else 0) and r["truncated"] == 0
+    assert r["blocks"] == r["tours"] * (len(B) - 1) and r["passes"] >= r["iters"] >= r["swaps"]
+    assert lll_oracle.matmul(B, r["U_out"]) == r["basis_out"]
+    if len(B) <= 33:
+        assert abs(lll_oracle.det_bareiss(r["U_out"])) == 1
+    if name in ("dense17", "dense33", "dense63"):
+        assert r["insertions"] > 0
+    if name == "dense17":
+        assert (r["tours"], r["blocks"], r["insertions"], r["nodes"]) == (6, 96, 23, 2243)
+    if name == "dense33":
+        assert (r["tours"], r["insertions"], r["nodes"]) == (7, 50, 16064)
+    if r["status"] == 0 and len(B) <= 17:
+        assert bkz_oracle.plain_tour_insertions(r["basis_out"], beta) == 0
+    if name.startswith("tie"):  # the LLL of the tie, which half-away rounding would change
+        assert r["basis_out"] == lll_oracle.reduced(name, 0.99)["basis_out"] and r["insertions"] == 0
+
+
+def test_schedule_counts_launches_and_suspensions():
+    """bkz_oracle.schedule on hand-made traces, slices of 16 iterations and 64 nodes."""
+    sch = lambda *trace: bkz_oracle.schedule({"trace": list(trace)}, 16, 64)  # noqa: E731
+    assert sch() == (1, 0, 0)  # stopped by chol(0): the launch that writes the outputs
+    assert sch(("lll", 16), ("enum", 64)) == (1, 0, 0)  # both budgets spent on the last steps
+    assert sch(("lll", 17)) == (2, 1, 0) and sch(("lll", 16), ("enum", 65)) == (2, 0, 1)
+    assert sch(("lll", 10), ("enum", 30), ("lll", 5), ("enum", 30), ("lll", 1), ("enum", 5)) == (2, 0, 1)
+    assert sch(("lll", 10), ("enum", 30), ("lll", 7), ("enum", 30)) == (2, 1, 0)
+    assert sch(("lll", 40), ("enum", 200)) == (3 + 3, 2, 3)
+    # the trace of a real run accounts for every iteration and node
+    r = bkz_oracle.reduced("dense17", 6)
+    assert sum(n for k, n in r["trace"] if k == "lll") == r["iters"]
+    assert sum(n for k, n in r["trace"] if k == "enum") == r["nodes"]
+    assert [n for k, n in r["trace"] if k == "enum"] == [g[2] for g in r["log"]]
+    assert sum(1 for k, _ in r["trace"] if k == "lll") == 1 + r["insertions"]
+
+
+def test_mixed_batch_is_suspended_in_both_phases():
+    """bkz_oracle.mixed_batch() at beta = 6 under 16 iterations and 64 nodes per launch: the
+    entries need different numbers of launches, at least one is suspended inside an LLL and at
+    least one inside an enumeration, and at MIXED_MAX_TOURS status 4, 0 and 3 meet in one call.
+    (No block of these bases takes more than 64 nodes -- nor did one of 360 other dense bases of
+    d = 17 at beta = 6 -- so an enumeration is suspended where a launch's 64 nodes run out in a
+    later block of a run of blocks without insertion: schedule() follows the kernel's budgets.)"""
+    B, R = bkz_oracle.mixed_batch(), bkz_oracle.mixed_reduced()
+    n = len(B)
+    assert B.shape == (n, 17, 17) and n == len(bkz_oracle.MIXED_DENSE) + 4
+    assert len({amp for _, amp in bkz_oracle.MIXED_DENSE}) == 3
+    sched = [bkz_oracle.schedule(r) for r in R]
+    print(f"  (launches, suspended in LLL, suspended in ENUM) per entry: {sched}")
+    assert len({s[0] for s in sched}) >= 5
+    assert sum(1 for s in sched if s[1] > 0) >= 3 and sum(1 for s in sched if s[2] > 0) >= 3
+    for r, s in zip(R, sched):  # the bounds the device test puts on the launch count hold entry by entry
+        li, ln = -(-r["iters"] // bkz_oracle.LLL_SLICE), -(-r["nodes"] // bkz_oracle.BKZ_SLICE)
+        assert max(1, li, ln) <= s[0] <= 1 + li + ln
+    ident = [k for k in range(n) if np.array_equal(B[k], np.eye(17, dtype=np.int64))]
+    assert len(ident) == 1 and (R[ident[0]]["insertions"], R[ident[0]]["tours"], R[ident[0]]["swaps"]) == (0, 1, 0)
+    red = [k for k in range(n) if B[k].tolist() == R[0]["basis_out"]]
+    assert len(red) == 1 and R[0]["insertions"] > 0
+    assert (R[red[0]]["insertions"], R[red[0]]["tours"], R[red[0]]["status"], R[red[0]]["swaps"]) == (0, 1, 0, 0)
+    sing = [k for k in range(n) if R[k]["status"] == 3]
+    assert len(sing) == 1 and 0 < sing[0] < n - 1 and lll_oracle.det_bareiss(B[sing[0]].tolist()) == 0
+    assert all(r["status"] == 0 for k, r in enumerate(R) if k not in sing)
+    same = [(i, j) for i in range(n) for j in range(i + 1, n) if np.array_equal(B[i], B[j])]
+    assert len(same) == 1 and R[same[0][0]] == R[same[0][1]]
+    cut = bkz_oracle.mixed_reduced(bkz_oracle.MIXED_MAX_TOURS)
+    st = [r["status"] for r in cut]
+    assert st.count(4) >= 2 and st.count(0) >= 2 and st.count(3) == 1
+    assert all(r["tours"] == bkz_oracle.MIXED_MAX_TOURS for r in cut if r["status"] == 4)
+
+
+def test_chunk_batch_under_bkz():
+    """lll_oracle.chunk_batch() at beta = 2: the singular entries at the chunk boundary stop with
+    status 3 before any tour, every other entry ends with status 0, and the LLL of each is
+    lll_oracle's (no block of two holds a shorter vector after LLL at 0.99 here)."""
+    R, L = bkz_oracle.chunk_reduced(), lll_oracle.chunk_reduced()
+    assert sorted(R) == sorted(L) and (R[-1]["status"], R[-2]["status"]) == (3, 3)
+    assert R[-1]["tours"] == R[-2]["tours"] == 0
+    for v in range(lll_oracle.CHUNK_DISTINCT):
+        assert R[v]["status"] == 0 and R[v]["tours"] >= 1 and R[v]["blocks"] == 2 * R[v]["tours"]
+        if R[v]["insertions"] == 0:
+            assert all(R[v][f] == L[v][f] for f in ("basis_out", "U_out", "iters", "swaps", "passes", "gs_norm2"))
+    for part in (lll_oracle.chunk_batch()[1][:1024], lll_oracle.chunk_batch()[1][1024:]):
+        assert len({bkz_oracle.schedule(R[v], 2, 1 << 16)[0] for v in part}) >= 2

@@ -1,7 +1,9 @@
 """lgs_bkz_reduce on the device against the Python transcription of its definition
 (tests/bkz_oracle.py): every output bit for bit, whatever the batch, the split into calls, the
 pointer kind or the launch slices; the stops (enum_nodes, max_tours, max_iters, the magnitude
-guard of INSERT, not a basis, bad input); and the public layers end to end.
+guard of INSERT, not a basis, bad input); the public layers end to end; dense signed bases at
+ragged d and the rounding ties; and the scheduler -- a mixed batch suspended inside LLL runs and
+inside enumerations over many launches, and more bases than one chunk.
 tests/test_bkz_host.py checks the premises on the oracle."""
 import math
 
@@ -258,3 +260,167 @@ def test_public_layers_end_to_end(ctx):
     _, _, dl = lr.lll_reduce(rows32, delta=0.99)
     assert d12["final_quality"]["max_gs_norm"] <= dl["final_quality"]["max_gs_norm"]
     assert np.array_equal(np.array(bkz_oracle.reduced("qary32", 12)["gs_norm2"]), d12["bkz"][0]["gs_norm2"])
+
+
+# ---------------------------------------------------------------- dense signed bases and rounding ties
+@pytest.mark.parametrize("name,beta,max_tours", bkz_oracle.DENSE_CASES)
+def test_parity_on_dense_signed_bases_and_ties(ctx, name, beta, max_tours):
+    """Dense bases with entries of both signs at d = 7, 17, 33 and 63, and the two 2 x 2 bases whose
+    first mu is +-2.5 (lll_loop is shared: half-away rounding would return another basis)."""
+    B = bkz_oracle.basis(name)
+    want = bkz_oracle.reduced(name, beta, max_tours=max_tours)
+    got = _run(ctx, B[None], beta, max_tours=max_tours)
+    print(f"  {name} beta {beta}: status {got['status'][0]}, tours {got['tours'][0]}, insertions "
+          f"{got['insertions'][0]} (oracle {want['insertions']}), nodes {got['nodes'][0]} (oracle {want['nodes']}), "
+          f"iters {got['iters'][0]} (oracle {want['iters']})")
+    _equal(got, 0, want, (name, beta))
+    assert np.array_equal(B @ got["U_out"][0], got["basis_out"][0])
+
+
+def test_library_refuses_parameters_out_of_range_on_either_pointer_kind(capi, ctx):
+    """delta, eta and d outside their ranges, straight to the library (Context.bkz_reduce refuses
+    them before it): LGS_ERR_INVALID, and no output is touched, with host and with device pointers."""
+    import torch
+    bad = [dict(delta=v) for v in (0.25, 1.0, math.nan)] + [dict(eta=v) for v in (0.5, 1.0, math.nan)] + \
+        [dict(d=1), dict(d=65)]
+    for kw in bad:
+        d = kw.get("d", 4)
+        B = np.stack([np.eye(d, dtype=np.int64) * 3] * 2)
+        for dev in (False, True):
+            b = torch.as_tensor(B, device="cuda:0") if dev else B
+            bo, uo = (torch.full_like(b, -77) for _ in range(2)) if dev else (np.full_like(B, -77) for _ in range(2))
+            st = torch.full((2,), -1, dtype=torch.int32, device="cuda:0") if dev else np.full(2, -1, dtype=np.int32)
+            rc = ctx._L.lgs_bkz_reduce(ctx._h, 2, d, capi._ptr(b), 2, kw.get("delta", 0.99), kw.get("eta", 0.51), 4,
+                                       100, 100, capi._ptr(bo), capi._ptr(uo),
+                                       capi._outputs(capi.BkzOutputs, *([None] * 8), st, None),
+                                       capi.LGS_DEVICE_PTRS if dev else 0)
+            assert rc == capi.LGS_ERR_INVALID, (kw, dev)
+            word = next(iter(kw))
+            assert ("d = " if word == "d" else word) in ctx._L.lgs_last_error().decode(), (kw, dev)
+            if dev:
+                torch.cuda.synchronize()
+            assert bool((bo == -77).all()) and bool((uo == -77).all()) and bool((st == -1).all()), (kw, dev)
+    got = _run(ctx, np.eye(4, dtype=np.int64)[None] * 3, 2)  # the context still works
+    assert got["status"][0] == 0 and got["iters"][0] == 3
+
+
+# ---------------------------------------------------------------- the scheduler: batches across launches and chunks
+OPTIONAL = COUNTERS + ("status", "gs_norm2")
+
+
+def _device_run(capi, c, bd, beta, max_tours=1 << 40, only=OPTIONAL):
+    """The raw call on device buffers (bd a device tensor), the optional outputs named in `only`
+    requested and pre-filled like _run's; returns host arrays."""
+    import torch
+    n, d, dev = bd.shape[0], bd.shape[1], bd.device
+    out = {"basis_out": torch.full_like(bd, -77), "U_out": torch.full_like(bd, -77)}
+    for f in only:
+        out[f] = (torch.full((n, d), math.nan, dtype=torch.float64, device=dev) if f == "gs_norm2" else
+                  torch.full((n,), -1, dtype=torch.int32 if f == "status" else torch.int64, device=dev))
+    c.bkz_reduce(bd, out["basis_out"], out["U_out"], beta, max_tours=max_tours, flags=capi.LGS_DEVICE_PTRS,
+                 **{f: out[f] for f in only})
+    torch.cuda.synchronize()
+    return {f: t.cpu().numpy() for f, t in out.items()}
+
+
+def _host_run(c, bases, beta, only):
+    """_run with only the optional outputs named in `only`."""
+    b = np.ascontiguousarray(bases, dtype=np.int64)
+    n, d = b.shape[0], b.shape[1]
+    out = {"basis_out": np.full((n, d, d), -77, dtype=np.int64), "U_out": np.full((n, d, d), -77, dtype=np.int64)}
+    for f in only:
+        out[f] = (np.full((n, d), np.nan) if f == "gs_norm2" else
+                  np.full(n, -1, dtype=np.int32 if f == "status" else np.int64))
+    c.bkz_reduce(b, out["basis_out"], out["U_out"], beta, **{f: out[f] for f in only})
+    return out
+
+
+def _equal_all(got, wants, what):
+    """Every entry of a batched result against its own oracle result, whole arrays at a time."""
+    conv = {id(o): bkz_oracle.as_arrays(o) for o in wants}
+    for f in got:
+        w = np.stack([conv[id(o)][f] for o in wants])
+        assert got[f].dtype == w.dtype and got[f].shape == w.shape, (what, f)
+        diff = np.flatnonzero((got[f].view(np.int64) != w.view(np.int64)).reshape(len(wants), -1).any(axis=1)) \
+            if f == "gs_norm2" else np.flatnonzero((got[f] != w).reshape(len(wants), -1).any(axis=1))
+        assert diff.size == 0, (what, f, "entries", diff[:8], got[f][diff[0]], w[diff[0]])
+
+
+def _launches(c, capi):
+    return c.timing_get(capi.KERNEL_CVP_ENUM)[1]
+
+
+def _bounds(wants, lll_slice, node_slice):
+    """least and most of test_forced_slices_span_launches, the max over the batch in place of one basis."""
+    li = [-(-w["iters"] // lll_slice) for w in wants]
+    ln = [-(-w["nodes"] // node_slice) for w in wants]
+    return 1 + max(max(1, a, b) for a, b in zip(li, ln)), max(2 + a + b for a, b in zip(li, ln))
+
+
+@pytest.mark.parametrize("max_tours", [1 << 40, bkz_oracle.MIXED_MAX_TOURS])
+def test_mixed_batch_spans_launches(capi, monkeypatch, max_tours):
+    """bkz_oracle.mixed_batch() -- ten bases of d = 17 at beta = 6, suspended inside LLL runs and
+    inside enumerations a different number of times each, the early leavers in the middle of the
+    batch -- on the hooks library at LLL_SLICE iterations and BKZ_SLICE nodes per launch: every
+    field of every entry equals its own oracle, counters included, with host and device pointers;
+    with max_tours = MIXED_MAX_TOURS status 4, 0 and 3 meet in one call.  Timer 9 lies within the
+    bounds of the single-basis test, and equals the set-up launch plus the launches
+    bkz_oracle.schedule derives from the kernel's two budgets for the entry that needs most."""
+    import torch
+    monkeypatch.setenv("LGS_TEST_BKZ_SLICE", str(bkz_oracle.BKZ_SLICE))
+    monkeypatch.setenv("LGS_TEST_LLL_SLICE", str(bkz_oracle.LLL_SLICE))
+    hctx = capi.Context(0, hooks=True)
+    B, want = bkz_oracle.mixed_batch(), bkz_oracle.mixed_reduced(max_tours)
+    least, most = _bounds(want, bkz_oracle.LLL_SLICE, bkz_oracle.BKZ_SLICE)
+    exact = 1 + max(bkz_oracle.schedule(w)[0] for w in want)
+    hctx.timing_enable(True)
+    got = _run(hctx, B, bkz_oracle.MIXED_BETA, max_tours=max_tours)
+    launches = _launches(hctx, capi)
+    print(f"  max_tours {max_tours}: {launches} launches (between {least} and {most}, schedule {exact}), "
+          f"status {list(got['status'])}")
+    _equal_all(got, want, "host")
+    for k, w in enumerate(want):
+        _equal(got, k, w, ("host", k))
+    assert 3 < least <= launches <= most and launches == exact
+    bd = torch.as_tensor(B, device="cuda:0")
+    hctx.timing_enable(True)
+    gd = _device_run(capi, hctx, bd, bkz_oracle.MIXED_BETA, max_tours)
+    assert _launches(hctx, capi) == launches
+    _equal_all(gd, want, "device")
+    assert torch.equal(bd, torch.as_tensor(B, device="cuda:0"))  # the input is not written
+    _equal_all(_device_run(capi, hctx, bd.flip(0).contiguous(), bkz_oracle.MIXED_BETA, max_tours), want[::-1],
+               "device, reversed")
+    hctx.close()
+
+
+@pytest.mark.parametrize("library,dev", [("product", False), ("product", True), ("hooks", False), ("hooks", True)])
+def test_more_bases_than_one_chunk(capi, monkeypatch, library, dev):
+    """lll_oracle.chunk_batch() at beta = 2: 1030 bases of d = 3, six more than the scheduler's
+    chunk, a singular one on either side of the boundary.  Every optional output at once, then
+    status alone, then gs_norm2 alone (each offset is its own code); on the hooks library two LLL
+    iterations per launch, so that the second chunk's live list spans launches too.  Timer 9: per
+    chunk the set-up launch and the launches of the entry that needs most."""
+    import torch
+    lll_slice = 1 << 12
+    if library == "hooks":
+        lll_slice = 2
+        monkeypatch.setenv("LGS_TEST_LLL_SLICE", "2")
+    c = capi.Context(0, hooks=library == "hooks")
+    B, idx = lll_oracle.chunk_batch()
+    B0 = B.copy()
+    R = bkz_oracle.chunk_reduced()
+    want = [R[v] for v in idx]
+    parts = ([R[v] for v in idx[:1024]], [R[v] for v in idx[1024:]])
+    least, most = (sum(x) for x in zip(*(_bounds(p, lll_slice, 1 << 16) for p in parts)))
+    exact = sum(1 + max(bkz_oracle.schedule(w, lll_slice, 1 << 16)[0] for w in p) for p in parts)
+    assert (least == exact == 4) if library == "product" else (exact > 8)
+    bd = torch.as_tensor(B, device="cuda:0") if dev else None
+    for only in (OPTIONAL, ("status",), ("gs_norm2",)):
+        c.timing_enable(True)
+        got = _device_run(capi, c, bd, 2, only=only) if dev else _host_run(c, B, 2, only)
+        launches = _launches(c, capi)
+        assert least <= launches <= most and launches == exact, (only, launches, least, most, exact)
+        assert sorted(got) == sorted(("basis_out", "U_out") + tuple(only))
+        _equal_all(got, want, (library, dev, only))
+    assert np.array_equal(bd.cpu().numpy() if dev else B, B0)  # the input is not written
+    c.close()

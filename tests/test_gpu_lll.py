@@ -1,9 +1,12 @@
 """lgs_lll_reduce on the device against the Python transcription of its definition
 (tests/lll_oracle.py): every output bit for bit, whatever the batch, the split into calls, the
 pointer kind or the launch slice; the stops (max_iters, magnitude guard, not a basis, bad
-input); and the reduce=True paths of SimpleLattice end to end.  tests/test_lll_host.py checks
-the premises on the oracle (it terminates with work done on every basis used here, and its
-iteration counts lie on both sides of the forced slice)."""
+input); the reduce=True paths of SimpleLattice end to end; dense signed bases at ragged d and
+three (delta, eta), rounding ties and Gram entries that fp64 cannot hold; and the scheduler --
+a mixed batch whose live list shrinks with holes over many launches, and more bases than one
+chunk.  tests/test_lll_host.py checks the premises on the oracle (it terminates with work done
+on every basis used here, its iteration counts lie on both sides of the forced slice, the
+batches spread over the launches and cross the chunk the source names)."""
 import itertools
 import math
 
@@ -263,3 +266,177 @@ def test_simple_lattice_reduce_end_to_end():
     m2 = lat.lll().gaussian_mass(3.0, center=c, nats=6.0, moments=True)
     assert m1["status"] == 0 and m1["points"] == m2["points"] >= 1 and m1["log_mass"] == m2["log_mass"]
     assert np.allclose(m1["mean_z"] @ rows, m2["mean_z"] @ red.astype(np.float64), rtol=0, atol=1e-9)
+
+
+# ---------------------------------------------------------------- dense signed bases, rounding ties, large Gram
+@pytest.mark.parametrize("name,delta,eta", lll_oracle.DENSE_CASES)
+def test_parity_on_dense_signed_bases(ctx, name, delta, eta):
+    """Dense bases with entries of both signs at the d where the ownership of lanes changes (5, 7,
+    17, 33, 63, 64), at three (delta, eta) whose iteration counts differ (test_lll_host.py)."""
+    B = lll_oracle.bases()[name]
+    got = _run(ctx, B[None], delta, eta)
+    want = lll_oracle.reduced(name, delta, eta=eta)
+    print(f"  {name} ({delta}, {eta}): iters {got['iters'][0]} (oracle {want['iters']}), swaps {got['swaps'][0]}, "
+          f"status {got['status'][0]}")
+    _equal(got, 0, want, (name, delta, eta))
+    assert np.array_equal(B @ got["U_out"][0], got["basis_out"][0])
+
+
+@pytest.mark.parametrize("name", lll_oracle.TIE_NAMES + lll_oracle.BIG_NAMES)
+def test_parity_on_rounding_ties_and_gram_entries_above_2_to_53(ctx, name):
+    """mu[1][0] exactly 2.5, -2.5, 3.5, 1.5: the size reduction rounds half to even (the first two
+    give another basis under half-away, test_lll_host.py).  big4, big9: Gram entries of 55 and more
+    bits, whose conversion to fp64 rounds; big9 trips the magnitude guard in iteration 30."""
+    B = lll_oracle.bases()[name]
+    got = _run(ctx, np.stack([B, B]))
+    want = lll_oracle.reduced(name, 0.99)
+    print(f"  {name}: iters {got['iters'][0]} (oracle {want['iters']}), status {got['status'][0]}")
+    _equal(got, 0, want, name)
+    _equal(got, 1, want, name)
+    assert np.array_equal(B @ got["U_out"][0], got["basis_out"][0])
+
+
+def test_library_refuses_parameters_out_of_range_on_either_pointer_kind(capi, ctx):
+    """delta, eta and d outside their ranges, straight to the library (Context.lll_reduce refuses
+    them before it): LGS_ERR_INVALID, and no output is touched, with host and with device pointers."""
+    import torch
+    bad = [dict(delta=v) for v in (0.25, 1.0, math.nan)] + [dict(eta=v) for v in (0.5, 1.0, math.nan)] + \
+        [dict(d=1), dict(d=65)]
+    for kw in bad:
+        d = kw.get("d", 4)
+        B = np.stack([np.eye(d, dtype=np.int64) * 3] * 2)
+        for dev in (False, True):
+            b = torch.as_tensor(B, device="cuda:0") if dev else B
+            bo, uo = (torch.full_like(b, -77) for _ in range(2)) if dev else (np.full_like(B, -77) for _ in range(2))
+            st = torch.full((2,), -1, dtype=torch.int32, device="cuda:0") if dev else np.full(2, -1, dtype=np.int32)
+            rc = ctx._L.lgs_lll_reduce(ctx._h, 2, d, capi._ptr(b), kw.get("delta", 0.99), kw.get("eta", 0.51), 100,
+                                       capi._ptr(bo), capi._ptr(uo),
+                                       capi._outputs(capi.LllOutputs, None, None, None, st, None),
+                                       capi.LGS_DEVICE_PTRS if dev else 0)
+            assert rc == capi.LGS_ERR_INVALID, (kw, dev)
+            word = next(iter(kw))
+            assert ("d = " if word == "d" else word) in ctx._L.lgs_last_error().decode(), (kw, dev)
+            if dev:
+                torch.cuda.synchronize()
+            assert bool((bo == -77).all()) and bool((uo == -77).all()) and bool((st == -1).all()), (kw, dev)
+    got = _run(ctx, np.eye(4, dtype=np.int64)[None] * 3)  # the context still works
+    assert got["status"][0] == 0 and got["iters"][0] == 3
+
+
+# ---------------------------------------------------------------- the scheduler: batches across launches and chunks
+def _device_run(capi, c, bd, delta=0.99, eta=0.51, max_iters=1 << 40, only=FIELDS[2:]):
+    """The raw call on device buffers (bd a device tensor), the optional outputs named in `only`
+    requested and pre-filled like _run's; returns host arrays."""
+    import torch
+    n, d, dev = bd.shape[0], bd.shape[1], bd.device
+    out = {"basis_out": torch.full_like(bd, -77), "U_out": torch.full_like(bd, -77)}
+    for f in only:
+        out[f] = (torch.full((n, d), math.nan, dtype=torch.float64, device=dev) if f == "gs_norm2" else
+                  torch.full((n,), -1, dtype=torch.int32 if f == "status" else torch.int64, device=dev))
+    c.lll_reduce(bd, out["basis_out"], out["U_out"], delta, eta, max_iters, flags=capi.LGS_DEVICE_PTRS,
+                 **{f: out[f] for f in only})
+    torch.cuda.synchronize()
+    return {f: t.cpu().numpy() for f, t in out.items()}
+
+
+def _host_run(c, bases, only):
+    """_run with only the optional outputs named in `only`."""
+    b = np.ascontiguousarray(bases, dtype=np.int64)
+    n, d = b.shape[0], b.shape[1]
+    out = {"basis_out": np.full((n, d, d), -77, dtype=np.int64), "U_out": np.full((n, d, d), -77, dtype=np.int64)}
+    for f in only:
+        out[f] = (np.full((n, d), np.nan) if f == "gs_norm2" else
+                  np.full(n, -1, dtype=np.int32 if f == "status" else np.int64))
+    c.lll_reduce(b, out["basis_out"], out["U_out"], **{f: out[f] for f in only})
+    return out
+
+
+def _equal_all(got, wants, what):
+    """Every entry of a batched result against its own oracle result, whole arrays at a time."""
+    conv = {id(o): lll_oracle.as_arrays(o) for o in wants}
+    for f in got:
+        w = np.stack([conv[id(o)][f] for o in wants])
+        assert got[f].dtype == w.dtype and got[f].shape == w.shape, (what, f)
+        diff = np.flatnonzero((got[f].view(np.int64) != w.view(np.int64)).reshape(len(wants), -1).any(axis=1)) \
+            if f == "gs_norm2" else np.flatnonzero((got[f] != w).reshape(len(wants), -1).any(axis=1))
+        assert diff.size == 0, (what, f, "entries", diff[:8], got[f][diff[0]], w[diff[0]])
+
+
+def _launches(c, capi):
+    return c.timing_get(capi.KERNEL_CVP_ENUM)[1]
+
+
+def test_mixed_batch_spans_launches(capi, monkeypatch):
+    """lll_oracle.mixed_batch() -- 29 bases of d = 17 whose reductions need 1 to 24 launches of
+    SLICE iterations, the early leavers in the middle of the batch -- on the hooks library: every
+    entry equals its own oracle whatever list of live bases the launches pass on, with host and
+    device pointers, reversed, split into single calls, and with a budget that stops some entries
+    (status 1) while others end (0) or fail (3).  Timer 9 counts the set-up launch and the
+    reduction launches of the entry that needs most: max(1, ceil(iters / SLICE)) each, since
+    lll_loop sees k = d, and iters = max_iters, before it looks at the launch's budget."""
+    import torch
+    monkeypatch.setenv("LGS_TEST_LLL_SLICE", str(lll_oracle.SLICE))
+    hctx = capi.Context(0, hooks=True)
+    B, want = lll_oracle.mixed_batch(), lll_oracle.mixed_reduced()
+    count = 1 + max(lll_oracle.launches(w) for w in want)
+    hctx.timing_enable(True)
+    got = _run(hctx, B)
+    assert _launches(hctx, capi) == count
+    _equal_all(got, want, "host")
+    for k, w in enumerate(want):
+        _equal(got, k, w, ("host", k))
+    hctx.timing_enable(True)
+    _equal_all(_run(hctx, B[::-1]), want[::-1], "reversed")
+    assert _launches(hctx, capi) == count
+    bd = torch.as_tensor(B, device="cuda:0")
+    hctx.timing_enable(True)
+    gd = _device_run(capi, hctx, bd)
+    assert _launches(hctx, capi) == count
+    _equal_all(gd, want, "device")
+    assert torch.equal(bd, torch.as_tensor(B, device="cuda:0"))  # the input is not written
+    _equal_all(_device_run(capi, hctx, bd.flip(0).contiguous()), want[::-1], "device, reversed")
+    bo1, uo1 = torch.full_like(bd, -77), torch.full_like(bd, -77)
+    for k in range(len(B)):  # the split into single calls, on slices of the device buffers
+        hctx.lll_reduce(bd[k:k + 1], bo1[k:k + 1], uo1[k:k + 1], flags=capi.LGS_DEVICE_PTRS)
+    torch.cuda.synchronize()
+    assert np.array_equal(bo1.cpu().numpy(), gd["basis_out"]) and np.array_equal(uo1.cpu().numpy(), gd["U_out"])
+    # a budget between the entries' iteration counts
+    cut = lll_oracle.mixed_reduced(lll_oracle.MIXED_MAX_ITERS)
+    count = 1 + max(lll_oracle.launches(w) for w in cut)
+    hctx.timing_enable(True)
+    _equal_all(_run(hctx, B, max_iters=lll_oracle.MIXED_MAX_ITERS), cut, "max_iters, host")
+    assert _launches(hctx, capi) == count
+    hctx.timing_enable(True)
+    _equal_all(_device_run(capi, hctx, bd, max_iters=lll_oracle.MIXED_MAX_ITERS), cut, "max_iters, device")
+    assert _launches(hctx, capi) == count
+    hctx.close()
+
+
+@pytest.mark.parametrize("library,dev", [("product", False), ("product", True), ("hooks", False), ("hooks", True)])
+def test_more_bases_than_one_chunk(capi, monkeypatch, library, dev):
+    """lll_oracle.chunk_batch(): 1030 bases of d = 3, six more than the scheduler's chunk, a
+    singular one on either side of the boundary.  Every optional output at once, then status
+    alone, then gs_norm2 alone (each offset is its own code); on the hooks library two iterations
+    per launch, so that the second chunk's live list spans launches too.  Timer 9: per chunk the
+    set-up launch and the reduction launches of the entry that needs most."""
+    import torch
+    slice_ = 1 << 12
+    if library == "hooks":
+        slice_ = 2
+        monkeypatch.setenv("LGS_TEST_LLL_SLICE", "2")
+    c = capi.Context(0, hooks=library == "hooks")
+    B, idx = lll_oracle.chunk_batch()
+    B0 = B.copy()
+    R = lll_oracle.chunk_reduced()
+    want = [R[v] for v in idx]
+    count = sum(1 + max(lll_oracle.launches(R[v], slice_) for v in part) for part in (idx[:1024], idx[1024:]))
+    assert (count == 4) if library == "product" else (count > 8)
+    bd = torch.as_tensor(B, device="cuda:0") if dev else None
+    for only in (FIELDS[2:], ("status",), ("gs_norm2",)):
+        c.timing_enable(True)
+        got = _device_run(capi, c, bd, only=only) if dev else _host_run(c, B, only)
+        assert _launches(c, capi) == count, only
+        assert sorted(got) == sorted(("basis_out", "U_out") + tuple(only))
+        _equal_all(got, want, (library, dev, only))
+    assert np.array_equal(bd.cpu().numpy() if dev else B, B0)  # the input is not written
+    c.close()

@@ -268,3 +268,130 @@ def test_oracle_output_is_reduced_in_exact_arithmetic(name, delta):
     mu_x, lov = lll_oracle.gso_excess(r["basis_out"], delta, 0.51)
     print(f"  {name} delta {delta}: max |mu| - eta = {float(mu_x):.3e}, max Lovasz deficit = {float(lov):.3e}")
     assert mu_x <= 16 * MEASURED_MU_EXCESS and lov <= 16 * MEASURED_LOVASZ_DEFICIT
+
+
+# ---------------------------------------------------------------- premises of the dense, tie and large-Gram cases
+@pytest.mark.parametrize("name", lll_oracle.DENSE_NAMES)
+def test_dense_signed_bases_tell_the_parameters_apart(name):
+    """The dense bases are dense and signed; at every pair of lll_oracle.DENSE_PARAMS the oracle
+    ends with status 0 on a unimodular transform whose output is reduced in exact arithmetic (the
+    slack of the q-ary cases: none); and from d = 7 on the three pairs take three different
+    iteration counts, so a kernel that ignored delta or eta could not pass all three."""
+    B = lll_oracle.bases()[name]
+    d = B.shape[0]
+    assert d == dict((n, dd) for n, dd, _ in lll_oracle.DENSE)[name] and d % 2 == (name != "dense64")
+    assert np.count_nonzero(B) > 0.9 * d * d and (B < 0).sum() > d * d // 3 < (B > 0).sum()
+    assert lll_oracle.det_bareiss(B.tolist()) != 0
+    iters = []
+    for delta, eta in lll_oracle.DENSE_PARAMS:
+        r = lll_oracle.reduced(name, delta, eta=eta)
+        assert r["status"] == 0 and r["passes"] >= r["iters"] >= r["swaps"]
+        assert r["swaps"] > 0 or delta == 0.3  # (the lax pair leaves the small bases their order)
+        assert lll_oracle.matmul(B.tolist(), r["U_out"]) == r["basis_out"]
+        mu_x, lov = lll_oracle.gso_excess(r["basis_out"], delta, eta)
+        print(f"  {name} ({delta}, {eta}): iters {r['iters']}, max |mu| - eta = {float(mu_x):.3e}, "
+              f"max Lovasz deficit = {float(lov):.3e}")
+        assert mu_x <= 16 * MEASURED_MU_EXCESS and lov <= 16 * MEASURED_LOVASZ_DEFICIT
+        iters.append(r["iters"])
+    if d >= 7:
+        assert len(set(iters)) == 3, iters
+    want = {"dense5": 16, "dense7": 36, "dense17": 391, "dense33": 873, "dense63": 2073, "dense64": 1994}
+    assert iters[0] == want[name]
+    if name == "dense17":
+        assert iters == [391, 20, 550]
+
+
+def test_rounding_ties_tell_half_even_from_half_away():
+    """mu[1][0] of each tie basis is exactly the tie its name says.  With the rounding replaced by
+    half-away-from-zero the oracle returns another basis for 2.5 and -2.5 (half-even rounds to
+    +-2, half-away to +-3) and the same for 3.5 and 1.5 (both round to +-4 and +-2): the first two
+    are the cases that can tell a kernel's rint from a round()."""
+    mu = {"tie2.5": 2.5, "tie-2.5": -2.5, "tie3.5": 3.5, "tie1.5": 1.5, "tie6/4": 1.5}
+    assert tuple(mu) == lll_oracle.TIE_NAMES
+    for name, m in mu.items():
+        B = lll_oracle.bases()[name].tolist()
+        G = lll_oracle.gram(B)
+        assert Fraction(G[1][0], G[0][0]) == Fraction(m) and float(G[1][0]) / float(G[0][0]) == m
+        even, away = lll_oracle.lll(B), lll_oracle.lll(B, rnd=lll_oracle.half_away)
+        assert even["status"] == away["status"] == 0 and even == lll_oracle.reduced(name, 0.99)
+        assert (even["basis_out"] != away["basis_out"]) == (abs(m) == 2.5), name
+    assert lll_oracle.reduced("tie2.5", 0.99)["basis_out"] == [[1, 1], [1, -1]]  # columns (1, 1), (1, -1)
+    away = lll_oracle.lll(lll_oracle.TIES["tie2.5"].tolist(), rnd=lll_oracle.half_away)
+    assert away["basis_out"] == [[-1, 1], [1, 1]]  # columns (-1, 1), (1, 1)
+    assert [lll_oracle.half_away(x) for x in (2.5, -2.5, 3.5, -1.5, 0.5, 2.4999, -0.75)] == [3, -3, 4, -2, 1, 2, -1]
+    assert [round(x) for x in (2.5, -2.5, 3.5, -1.5)] == [2, -2, 4, -2]
+
+
+def test_gram_entries_above_2_to_53_round_on_conversion():
+    """big4 ends with status 0 and big9 trips the magnitude guard late in its run; the Gram matrix
+    of each holds an entry of 2^53 or more that fp64 cannot represent, so (double)G[k][j] has to
+    round (to nearest even, as Python's float(int) does)."""
+    bb = lll_oracle.big_bases()
+    assert tuple(bb) == lll_oracle.BIG_NAMES and [bb[n].shape[0] for n in bb] == [4, 9]
+    r4, r9 = (lll_oracle.reduced(n, 0.99) for n in lll_oracle.BIG_NAMES)
+    assert (r4["status"], r4["iters"]) == (0, 15) and r9["status"] == 2 and r9["iters"] >= 30
+    for name, r in (("big4", r4), ("big9", r9)):
+        B = bb[name].tolist()
+        assert np.abs(bb[name]).max() < lll_oracle.B_LIMIT and (bb[name] < 0).any()
+        G = lll_oracle.gram(B)
+        inexact = [g for row in G for g in row if abs(g) >= 1 << 53 and int(float(g)) != g]
+        bits = max(G[i][i] for i in range(len(B))).bit_length()
+        print(f"  {name}: {len(inexact)} Gram entries round, largest diagonal {bits} bits")
+        assert inexact
+        assert lll_oracle.matmul(B, r["U_out"]) == r["basis_out"]
+    assert max(g.bit_length() for g in np.diag(np.array(lll_oracle.gram(bb["big4"].tolist()), dtype=object))) == 55
+
+
+# ---------------------------------------------------------------- premises of the scheduling tests
+def test_mixed_batch_spreads_over_the_launches():
+    """lll_oracle.mixed_batch() under SLICE iterations per launch: the entries need many different
+    numbers of launches, some leave the live list after the first and they do not all sit at the
+    end (the list gets holes), one needs twenty or more; and at MIXED_MAX_ITERS status 0, 1 and 3
+    meet in one call."""
+    B, R = lll_oracle.mixed_batch(), lll_oracle.mixed_reduced()
+    n = len(B)
+    assert B.shape == (n, 17, 17) and len(R) == n == 3 * len(lll_oracle.MIXED_SEEDS) + 5
+    need = [lll_oracle.launches(r) for r in R]
+    print(f"  launches per entry: {need}")
+    assert [lll_oracle.launches({"iters": i}, 16) for i in (0, 1, 16, 17, 32, 33)] == [1, 1, 1, 2, 2, 3]
+    assert len(set(need)) >= 5 and max(need) >= 20
+    first = [k for k, v in enumerate(need) if v == 1]
+    assert len(first) >= 2 and any(any(need[j] > 1 for j in range(k + 1, n)) for k in first)
+    assert max(first) < n - 1 and min(first) > 0
+    ident = [k for k in range(n) if np.array_equal(B[k], np.eye(17, dtype=np.int64))]
+    assert len(ident) == 1 and R[ident[0]]["iters"] == lll_oracle.SLICE and R[ident[0]]["swaps"] == 0
+    red = [k for k in range(n) if B[k].tolist() == lll_oracle.reduced("dense17", 0.99)["basis_out"]]
+    assert len(red) == 1 and R[red[0]]["swaps"] == 0 and R[red[0]]["U_out"] == R[ident[0]]["U_out"]
+    sing = [k for k in range(n) if R[k]["status"] == 3]
+    assert len(sing) == 2 and all(lll_oracle.det_bareiss(B[k].tolist()) == 0 for k in sing)
+    assert R[sing[0]]["iters"] == 1 and R[sing[1]]["iters"] > lll_oracle.SLICE  # at once; only at k >= 2
+    assert all(r["status"] == 0 for k, r in enumerate(R) if k not in sing)
+    same = [(i, j) for i in range(n) for j in range(i + 1, n) if np.array_equal(B[i], B[j])]
+    assert len(same) == 1 and R[same[0][0]] == R[same[0][1]]
+    cut = lll_oracle.mixed_reduced(lll_oracle.MIXED_MAX_ITERS)
+    st = [r["status"] for r in cut]
+    assert st.count(0) >= 3 and st.count(1) >= 3 and st.count(3) == 2
+    assert all(r["iters"] == lll_oracle.MIXED_MAX_ITERS for r in cut if r["status"] == 1)
+
+
+def test_chunk_batch_crosses_the_scheduler_s_chunk():
+    """kLllChunk is read out of the source: lll_oracle.chunk_batch() has more entries than one
+    chunk holds, a singular basis is the last of the first chunk and another the first of the
+    second, and the rest cycles 130 distinct bases (748 iterations in all)."""
+    kernels_h = open(os.path.join(CSRC, "lgs_kernels.h")).read()
+    m = re.search(r"constexpr int64_t kLllChunk = (\d+);", kernels_h)
+    assert m, "kLllChunk not in lgs_kernels.h"
+    chunk = int(m.group(1))
+    B, idx = lll_oracle.chunk_batch()
+    assert chunk < lll_oracle.CHUNK_N == len(B) == len(idx) < 2 * chunk and B.shape[1:] == (3, 3)
+    assert lll_oracle.CHUNK_SINGULAR == (chunk - 1, chunk) and (idx[chunk - 1], idx[chunk]) == (-1, -2)
+    R = lll_oracle.chunk_reduced()
+    assert sorted(R) == [-2, -1] + list(range(lll_oracle.CHUNK_DISTINCT))
+    assert R[-1]["status"] == R[-2]["status"] == 3
+    good = [R[v] for v in range(lll_oracle.CHUNK_DISTINCT)]
+    assert all(r["status"] == 0 for r in good) and sum(r["iters"] for r in good) == 748
+    assert len({tuple(map(tuple, B[k])) for k in range(lll_oracle.CHUNK_DISTINCT)}) == lll_oracle.CHUNK_DISTINCT
+    # both chunks hold entries that span launches at the slice of 2 that the device test forces
+    for part in (idx[:chunk], idx[chunk:]):
+        assert max(lll_oracle.launches(R[v], 2) for v in part) >= 3
+        assert len({lll_oracle.launches(R[v], 2) for v in part}) >= 2
